@@ -12,12 +12,18 @@ Metric (BASELINE.json): "Krylov iters/sec + SpMV GB/s (% HBM peak), cpminres 10M
             solution are HBM-resident, the factorization (ptime) and the shift are outside the
             timed region.
   value     Krylov iterations completed by all ranks / max over ranks of the timed wall time.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the line with the headline figures (metric, value, unit, ms_per_step, dtype, config, ...);
+`--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy.  Everything
+below takes runs of its own and is measured only with `--full` (null in a plain run's line):
   roofline  the dominant kernel, the triangular sweeps of one LDL' solve (a forward and a
             backward sweep, every round; an M*z runs two solves): algorithmic bytes / HIP-event-
             timed duration, vs 8 TB/s; spmv_roofline the same for the saddle-point SpMV
             r = x - Kp*y (the refinement residual inside every M*z).
   cpu_baseline  the C restatement (oracle/) of the same solve on the host, timed on a
             bounded sample of the same workload: one core, and OpenMP on the cores the box grants.
+  parity, exact_dots, pmc, passes, w4, s50   the comparisons with the oracle, the rocprofv3 counter
+            passes, config 5's per-pass rates and the two child runs.
 Multi-GPU (one process per GPU): ONE solve of the same S10 system row-block partitioned over
 the ranks (strong scaling): RCCL allreduce for the inner products,
 allgathered halos for the SpMVs and the separator exchange of the distributed LDL' sweeps.
@@ -52,6 +58,14 @@ def parse(argv=None):
                     help="print the launch plan (the torchrun command for --gpus N > 1) as JSON and exit")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the kernel rooflines, the CPU baseline and "
+                         "parity blocks, the exact_dots block, the rocprofv3 counter passes and the w4 / s50 child "
+                         "runs (the --no-* and --profile-reps options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64): xy, the solution "
+                         "[dx; dy] of rank 0's rows (a fixed seeded sample of it above 48 MB), resid_history and "
+                         "niters")
     ap.add_argument("--config", choices=("s10", "s50"), default="s10",
                     help="s10: symmetric 10M cpminres (the headline metric); s50: nonsymmetric 3x3-block "
                          "50M cpdqgmres(40) (SURVEY.md section 8d config 5)")
@@ -82,6 +96,8 @@ def parse(argv=None):
                     help="scale the rhs by (1 + eps*u), u uniform in [-1, 1] (sensitivity runs; never the bench line)")
     ap.add_argument("--perturb-seed", type=int, default=1)
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     s50 = a.config == "s50"
     if a.size is None:
         a.size = 50_000_000 if s50 else 10_000_000
@@ -274,54 +290,32 @@ def main(argv=None):
         dt = float(t.item())
     # one solve over all ranks: its iterations are the job's iterations (strong scaling)
     total_iters = float(iters)
+    if args.dump_outputs and rank == 0:
+        # before anything below calls step() again: xy and hist are the last timed step's
+        dump_outputs(args.dump_outputs, xy.cpu().numpy()[:N_loc], hist_gpu, niters_last)
 
-    prof = _lib.Profile()
-    _lib.check(_lib.lib.cpk_profile_kernels(ctx.h, A.h, Cm.h, M.h, args.profile_reps, C.byref(prof)))
+    ms_per_step = dt / args.steps * 1e3
+    value = total_iters / dt
     gbs = lambda byts, ms: byts / (ms * 1e-3) / 1e9  # noqa: E731
-    # the dominant kernel: the triangular sweeps of one LDL' solve (forward + backward, every
-    # round: sptrsv_pipe_kernel for round 0, sptrsv_upper_kernel above and sptrsv_last_kernel for
-    # the last round's forward + backward), 2 per M*z
-    sweep_ms, sweep_bytes = prof.fwd_ms + prof.bwd_ms, prof.fwd_bytes + prof.bwd_bytes
-    achieved = gbs(sweep_bytes, sweep_ms)
-    roofline = {"bound": "hbm", "kernel": "sptrsv_pipe_kernel (round 0) + sptrsv_upper_kernel / sptrsv_last_kernel "
-                                          "(upper rounds): one LDL' solve (forward + backward sweep, all rounds)",
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "bytes_per_launch": sweep_bytes,
-                # y = LDL^-1 x with y the output: since r04 v13 round 0 no longer stores the dead
-                # work vector, which the byte model dropped (8 B per round-0 row); the fraction on
-                # the r03/r04-v12 model (the solve's bytes plus that store) keeps rounds comparable
-                "frac_prev_model": round(gbs(sweep_bytes + prof.bwd_dead_store_bytes, sweep_ms) / HBM_PEAK_GBS, 4),
-                "avg_ms": round(sweep_ms, 5), "launches": int(prof.fwd_launches) + int(prof.bwd_launches)}
-    # the metric's "SpMV GB/s": the saddle-point SpMV inside every M*z (refinement residual)
-    spmv_achieved = gbs(prof.resid_bytes, prof.resid_ms)
-    spmv_roofline = {"kernel": "spmv_stream<EpiResidSched> (r = x - P'Kp P y, all in schedule order)",
-                     "achieved": round(spmv_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(spmv_achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "bytes_per_launch": prof.resid_bytes, "avg_ms": round(prof.resid_ms, 5)}
-    kernels = {k: {"avg_ms": round(getattr(prof, k + "_ms"), 5), "bytes": getattr(prof, k + "_bytes"),
-                   "GBps": round(gbs(getattr(prof, k + "_bytes"), getattr(prof, k + "_ms")), 1)}
-               for k in ("spmv", "resid", "fwd", "bwd", "apply")}
-    kernels["fwd"]["launches"], kernels["bwd"]["launches"] = int(prof.fwd_launches), int(prof.bwd_launches)
-    if prof.fwd_resid_ms > 0:  # the refinement's residual + forward sweep, fused (launch_sptrsv_fwd_resid)
-        kernels["fwd_resid"] = {"avg_ms": round(prof.fwd_resid_ms, 5), "bytes": prof.fwd_resid_bytes,
-                                "GBps": round(gbs(prof.fwd_resid_bytes, prof.fwd_resid_ms), 1),
-                                "replaces_ms": round(prof.resid_ms + prof.fwd_ms, 5)}
+    prof = roofline = spmv_roofline = kernels = None
+    if args.full:
+        prof, roofline, spmv_roofline, kernels = kernel_rooflines(ctx, A, Cm, M, args, gbs)
 
     passes = None
-    if rank == 0 and world == 1 and not distributed and args.config == "s50":
+    if args.full and rank == 0 and world == 1 and not distributed and args.config == "s50":
         passes = s50_passes(ctx, step, M, N, n, m, args, prof, gbs)
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not distributed:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not distributed:
         if args.config == "s50":
             cpu = cpu_baseline_s50(S, b1.cpu().numpy(), M, args)
         else:
             cpu, parity = cpu_baseline(S, b1.cpu().numpy(), M, args, hist_gpu, niters_last)
     exact = None
-    if rank == 0 and world == 1 and not distributed and not args.no_exact:
+    if args.full and rank == 0 and world == 1 and not distributed and not args.no_exact:
         exact = exact_block(ctx, S, M, step, st, hist, xy, b1, xy0, args, iters / dt)
     pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc and not distributed and args.config == "s10":
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not distributed and args.config == "s10":
         pmc = pmc_traffic(args)
         if pmc and pmc.get("resid"):
             spmv_roofline["traffic"] = pmc["resid"]["bytes"]
@@ -330,15 +324,13 @@ def main(argv=None):
         if pmc and pmc.get("fwd_resid") and "fwd_resid" in kernels:
             kernels["fwd_resid"]["traffic"] = pmc["fwd_resid"]["bytes"]
 
-    ms_per_step = dt / args.steps * 1e3
-    value = total_iters / dt
     if rank == 0:
         line = {
             "metric": ("Krylov iters/sec + SpMV GB/s (% HBM peak), cpminres 10M-dof, 1/2/4/8 GPU"
                        if args.config == "s10" else
                        "Krylov iters/sec, cpdqgmres(40) 50M-dof nonsymmetric 3x3-block"),
             "value": round(value, 2), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "full": args.full,
             "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic",
             "config": {"workload": (f"S10 synthetic symmetric saddle-point system, SURVEY 8d generator with B window "
@@ -374,7 +366,8 @@ def main(argv=None):
         }
         if passes is not None:
             line["passes"] = passes
-        if world == 1 and not distributed and args.config == "s10" and args.window == 64 and not args.no_sub:
+        if args.full and world == 1 and not distributed and args.config == "s10" and args.window == 64 \
+                and not args.no_sub:
             if not args.no_w4:
                 line["w4"] = sub_block(args, ["--window", "4"], "the S10 system with the +-4 B window (rounds 1-5's headline)")
             if not args.no_s50:
@@ -382,6 +375,58 @@ def main(argv=None):
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, xy, hist, niters):
+    """--dump-outputs: the arrays the last timed method call returned, as <path>/<name>.npy
+    (float64): xy, the solution [dx; dy] of the shifted system (whole up to 48 MB, else its
+    entries at 4 M sorted indices drawn once with a fixed seed, so two builds dump the same
+    entries), resid_history (the call's residual history) and niters."""
+    os.makedirs(path, exist_ok=True)
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.nbytes > 48 * 2**20:
+        idx = np.sort(np.random.default_rng(20240607).choice(xy.shape[0], size=4 * 2**20, replace=False))
+        xy = xy[idx]
+    np.save(os.path.join(path, "xy.npy"), xy)
+    np.save(os.path.join(path, "resid_history.npy"), np.asarray(hist, dtype=np.float64))
+    np.save(os.path.join(path, "niters.npy"), np.array([niters], dtype=np.float64))
+
+
+def kernel_rooflines(ctx, A, Cm, M, args, gbs):
+    """--full: the per-kernel profile (cpk_profile_kernels: --profile-reps HIP-event-timed launches
+    of each kernel) as the line's roofline, spmv_roofline and kernels blocks."""
+    from cpkrylov_amd import _lib
+    prof = _lib.Profile()
+    _lib.check(_lib.lib.cpk_profile_kernels(ctx.h, A.h, Cm.h, M.h, args.profile_reps, C.byref(prof)))
+    # the dominant kernel: the triangular sweeps of one LDL' solve (forward + backward, every
+    # round: sptrsv_pipe_kernel for round 0, sptrsv_upper_kernel above and sptrsv_last_kernel for
+    # the last round's forward + backward), 2 per M*z
+    sweep_ms, sweep_bytes = prof.fwd_ms + prof.bwd_ms, prof.fwd_bytes + prof.bwd_bytes
+    achieved = gbs(sweep_bytes, sweep_ms)
+    roofline = {"bound": "hbm", "kernel": "sptrsv_pipe_kernel (round 0) + sptrsv_upper_kernel / sptrsv_last_kernel "
+                                          "(upper rounds): one LDL' solve (forward + backward sweep, all rounds)",
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "bytes_per_launch": sweep_bytes,
+                # y = LDL^-1 x with y the output: since r04 v13 round 0 no longer stores the dead
+                # work vector, which the byte model dropped (8 B per round-0 row); the fraction on
+                # the r03/r04-v12 model (the solve's bytes plus that store) keeps rounds comparable
+                "frac_prev_model": round(gbs(sweep_bytes + prof.bwd_dead_store_bytes, sweep_ms) / HBM_PEAK_GBS, 4),
+                "avg_ms": round(sweep_ms, 5), "launches": int(prof.fwd_launches) + int(prof.bwd_launches)}
+    # the metric's "SpMV GB/s": the saddle-point SpMV inside every M*z (refinement residual)
+    spmv_achieved = gbs(prof.resid_bytes, prof.resid_ms)
+    spmv_roofline = {"kernel": "spmv_stream<EpiResidSched> (r = x - P'Kp P y, all in schedule order)",
+                     "achieved": round(spmv_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(spmv_achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                     "bytes_per_launch": prof.resid_bytes, "avg_ms": round(prof.resid_ms, 5)}
+    kernels = {k: {"avg_ms": round(getattr(prof, k + "_ms"), 5), "bytes": getattr(prof, k + "_bytes"),
+                   "GBps": round(gbs(getattr(prof, k + "_bytes"), getattr(prof, k + "_ms")), 1)}
+               for k in ("spmv", "resid", "fwd", "bwd", "apply")}
+    kernels["fwd"]["launches"], kernels["bwd"]["launches"] = int(prof.fwd_launches), int(prof.bwd_launches)
+    if prof.fwd_resid_ms > 0:  # the refinement's residual + forward sweep, fused (launch_sptrsv_fwd_resid)
+        kernels["fwd_resid"] = {"avg_ms": round(prof.fwd_resid_ms, 5), "bytes": prof.fwd_resid_bytes,
+                                "GBps": round(gbs(prof.fwd_resid_bytes, prof.fwd_resid_ms), 1),
+                                "replaces_ms": round(prof.resid_ms + prof.fwd_ms, 5)}
+    return prof, roofline, spmv_roofline, kernels
 
 
 def host_cpu():
@@ -571,7 +616,7 @@ def sub_block(args, extra, what):
     CPU sample, parity, exact-mode and PMC blocks), embedded in the headline line."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-sub"] + extra
+           "--full", "--no-sub"] + extra
     for flag in ("no_pmc", "no_cpu_baseline", "no_exact"):
         if getattr(args, flag):
             cmd.append("--" + flag.replace("_", "-"))

@@ -1,6 +1,7 @@
 """Convert the reference's two MATLAB example systems into compact, data-only CSR fixtures.
 
-Source (read as DATA only, never executed): /root/reference/examples/
+Source (read as DATA only, never executed): the reference's examples/ data files, kept beside
+this script:
   cvxqp1_m_2x2_symm_iter10.mat      (used by examples/cpk_exprog1.m:45-49, n = nH, m = nJ)
   cvxqp2_s_3x3_nonsymm_perm_iter10.mat (used by examples/cpk_exprog2.m:47-50, n = nH + nZ, m = nJ)
 
@@ -15,8 +16,8 @@ import scipy.io as sio
 import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
-REF = "/root/reference/examples"
 OUT = os.path.dirname(os.path.abspath(__file__))
+REF = OUT
 
 CASES = {
     # name: (mat file, function giving (n, m) from the header scalars)

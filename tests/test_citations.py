@@ -1,13 +1,13 @@
 """Every `<file>.m:N` / `<file>.m:N-M` citation in the product, oracle, tests and docs points at
-lines that exist in the cited reference file.  The file lengths are recorded here as data (the
-reference is not present on the GPU box); when /root/reference is present they are checked too."""
+lines that exist in the cited reference file.  The file lengths are recorded here as data, and
+checked against the line counts recorded from the reference itself
+(tests/golden/reference_line_counts.json)."""
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+RECORD = os.path.join(ROOT, "tests", "golden", "reference_line_counts.json")
 
 # line counts of the reference's MATLAB sources (lines, the last one unterminated counted)
 LENGTHS = {
@@ -52,14 +52,11 @@ def _citations():
 
 
 def test_lengths_match_reference():
-    if not os.path.isdir(REF):
-        pytest.skip("reference not present")
-    for dp, _, fs in os.walk(REF):
-        for f in fs:
-            if f.endswith(".m"):
-                with open(os.path.join(dp, f), errors="replace") as fh:
-                    n = sum(1 for _ in fh)
-                assert LENGTHS.get(f) == n, (f, n)
+    with open(RECORD) as fh:
+        recorded = json.load(fh)
+    assert sorted(recorded) == sorted(LENGTHS)  # every MATLAB source of the reference
+    for f, n in recorded.items():
+        assert LENGTHS.get(f) == n, (f, n)
 
 
 def test_citations_in_range():

@@ -3,8 +3,8 @@
 examples/cpk_exprog1.m:44-104 and cpk_exprog2.m:44-104 -- load, block cut (cpk_exprog1.m:62-67),
 reg_cpkrylov with the example options, the comparison with K \\ rhs.
 
-The reference's `.mat` files stay in /root/reference (they do not travel to the GPU box): the CPU
-test checks that load_mat reads them to exactly the arrays of the committed data fixtures
+The reference's two `.mat` data files are committed under tests/golden/: the CPU test checks
+that load_mat reads them to exactly the arrays of the committed data fixtures
 (tests/golden/make_fixtures.py), and the GPU test writes the fixture back as a MAT v5 file of the
 same variables (K, rhs, n, nH, nJ, nZ) and runs the drivers on it, against the oracle."""
 import importlib.util
@@ -19,8 +19,8 @@ import fixtures as F
 from oracle import oracle as O
 from sensitivity import band
 
-REF = "/root/reference/examples"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF = os.path.join(ROOT, "tests", "golden")
 FILES = {"cvxqp1_m": "cvxqp1_m_2x2_symm_iter10.mat", "cvxqp2_s": "cvxqp2_s_3x3_nonsymm_perm_iter10.mat"}
 FLOOR, SAFETY = 1e-8, 10.0
 
@@ -39,10 +39,7 @@ def _fixture_mat(name, path):
 def test_load_mat_reads_the_reference_files(name):
     """load_mat on the reference's own data files = the committed fixtures, bit for bit."""
     import cpkrylov_amd as cpk
-    path = os.path.join(REF, FILES[name])
-    if not os.path.exists(path):
-        pytest.skip("the reference is not in this container")
-    d = cpk.load_mat(path)
+    d = cpk.load_mat(os.path.join(REF, FILES[name]))
     z = np.load(os.path.join(ROOT, "tests", "golden", f"{name}.npz"), allow_pickle=False)
     K = d["K"]
     assert sp.isspmatrix_csr(K) and K.dtype == np.float64

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/abw
 export TMPDIR=/tmp
 ROUNDS=${ROUNDS:-2}
-ARGS=${BENCH_ARGS:---steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-exact --no-sub}
+ARGS=${BENCH_ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-exact --no-sub}
 for r in $(seq 1 $ROUNDS); do
   for spec in "$@"; do
     v=${spec%%:*}

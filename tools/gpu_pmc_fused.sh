@@ -1,6 +1,8 @@
 # S10 bench with its PMC passes (the fused residual sweep's traffic included), no CPU baseline
+# Output: $OUT/bench_pmc.json (default build/bench_pmc/)
 set -e
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+OUT=${OUT:-build/bench_pmc}
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 500 python bench.py --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/bench_pmc.json 2> gpurun_out/bench_pmc.err
+timeout -k 10 500 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/bench_pmc.json" 2> "$OUT/bench_pmc.err"
