@@ -132,7 +132,12 @@ std::vector<int32_t> min_degree(const HCsr &g) {
     std::vector<char> dead(nv, 0);
     std::vector<int32_t> order;
     order.reserve(nv);
-    std::vector<int32_t> mark(nv, -1), merged;
+    // mark[w] == stamp: w is already in the list being merged.  One stamp per update (a node is
+    // updated once for every eliminated neighbour, and a mark keyed by the node itself would
+    // survive from one of its updates into the next and drop its live neighbours)
+    std::vector<int64_t> mark(nv, -1);
+    std::vector<int32_t> merged;
+    int64_t stamp = 0;
     while (!pq.empty()) {
         int32_t v = pq.begin()->second;
         pq.erase(pq.begin());
@@ -145,10 +150,11 @@ std::vector<int32_t> min_degree(const HCsr &g) {
             pq.erase({(int64_t)adj[u].size(), u});
             // adj[u] <- (adj[u] U nb) \ {u, v, dead}
             merged.clear();
+            stamp++;
             for (int32_t w : adj[u])
-                if (!dead[w] && mark[w] != u) mark[w] = u, merged.push_back(w);
+                if (!dead[w] && mark[w] != stamp) mark[w] = stamp, merged.push_back(w);
             for (int32_t w : nb)
-                if (w != u && mark[w] != u) mark[w] = u, merged.push_back(w);
+                if (w != u && mark[w] != stamp) mark[w] = stamp, merged.push_back(w);
             adj[u].swap(merged);
             pq.insert({(int64_t)adj[u].size(), u});
         }

@@ -102,7 +102,10 @@ def dist_spmv(pl, kind, xloc, recv):
     """local rows of K*x with ghosts read from the allgathered halo buffer"""
     ptr, col, val = pl[kind + "_ptr"], pl[kind + "_col"], pl[kind + "_val"]
     nloc = pl["N_loc"]
-    xv = np.where(col < nloc, xloc[np.minimum(col, nloc - 1)], recv[np.maximum(col - nloc, 0)])
+    own = col < nloc
+    xv = np.empty(len(col))  # a rank may own nothing, or have nothing to receive
+    xv[own] = xloc[col[own]]
+    xv[~own] = recv[col[~own] - nloc]
     return seq_rowsum(ptr, val * xv)
 
 

@@ -51,6 +51,9 @@ def _system(name):
     if name == "synthetic20k":
         S = saddle_system(N=20000, seed=3)
         return dict(Q=S["Q"], B=S["B"], C=S["C"], G=S["G"], n=S["n"], m=S["m"], rhs=S["rhs"])
+    if name == "dense_col":
+        import structures
+        return structures.get(name)
     return F.load(name)
 
 
@@ -84,8 +87,13 @@ def test_dist_apply_bitexact(name, P, props):
         assert np.all(d[:nl] < S["n"]) and np.all(d[nl:] >= S["n"])
 
 
-@pytest.mark.parametrize("P", [1, 2, 4])
-@pytest.mark.parametrize("name", ["cvxqp1_m", "synthetic20k"])
+# cvxqp1_m at P = 2, 4 had a chain on a rank only while the minimum-degree ordering was wrong (a
+# 489-deep tree); with the tree 96 deep no rank's share has two upper rounds.  dense_col's clique
+# (tests/structures.py) is a dense chain on the rank that holds it under any ordering.  The
+# bit comparison of cvxqp1_m at P = 2, 4 with these small blocks, without the chain assertion,
+# is test_gpu_structures.test_dist_apply_small_blocks_cvxqp1_m.
+@pytest.mark.parametrize("name,P", [("cvxqp1_m", 1), ("synthetic20k", 1), ("synthetic20k", 2), ("synthetic20k", 4),
+                                    ("dense_col", 1), ("dense_col", 2), ("dense_col", 4)])
 def test_dist_apply_sweep_chain_bitexact(name, P):
     """The sweep chains on a distributed preconditioner: each rank's forward upper rounds in one
     launch (kChainFwd, before the separator exchange) and its backward upper rounds in one launch
