@@ -300,7 +300,18 @@ class opLDL2:
         return self
 
     T = property(transpose)
-    ctranspose = transpose
+
+    def ctranspose(self):  # opLDL2.m:134-136: M' is the bare factor composite, not M
+        return opLDL2Factor(self)
+
+    H = property(ctranspose)
+    conj = ctranspose  # opLDL2.m:127-129: the same composite
+
+    def multi_info(self):
+        """Diagnostic: the multi-column sweep of M' as launched (cpk_pc_multi_info)."""
+        v = (C.c_int64 * 4)()
+        check(lib.cpk_pc_multi_info(self.h, v))
+        return dict(zip(("kp", "launches", "staged_blocks", "direct_blocks"), list(v)))
 
     def to_dense(self):  # double(op), opLDL2.m:138-149
         e = np.zeros(self.n)
@@ -350,6 +361,57 @@ class opLDL2:
         if getattr(self, "h", None):
             lib.cpk_pc_destroy(self.h)
             self.h = None
+
+
+class opLDL2Factor:
+    """M' and conj(M) of an opLDL2: the bare factor composite P*L'^-1*D^-1*L^-1*P'
+    (opLDL2.m:127-136), applied once -- no refinement, no residual update, none of M's properties
+    read or written.  It shares M's handle and keeps M alive.  Unlike M it takes a block of
+    right-hand sides: `F @ X` with an N x k array solves the k columns in panels, streaming the
+    factor once per panel (cpk_pc_apply_ldl_multi); each column equals `F * X[:, j]` bit for bit."""
+
+    def __init__(self, parent):
+        self.parent = parent
+        self.n = parent.n
+        self.shape = parent.shape
+
+    def __mul__(self, z):
+        z = np.asarray(z, dtype=np.float64)
+        h = self.parent.h
+        if z.ndim == 2:
+            if z.shape[0] != self.n:
+                raise CpkError(_lib.CPK_ERR_DIM, "Dimensions do not match")
+            X = np.asfortranarray(z)
+            Y = np.empty((self.n, z.shape[1]), order="F")
+            if z.shape[1]:
+                check(lib.cpk_pc_apply_ldl_multi(h, z.shape[1], _dptr(X), max(self.n, 1), _dptr(Y), max(self.n, 1)))
+            return Y
+        z = np.ascontiguousarray(z).ravel()
+        if z.shape[0] != self.n:
+            raise CpkError(_lib.CPK_ERR_DIM, "Dimensions do not match")
+        y = np.empty(self.n)
+        check(lib.cpk_pc_apply_ldl(h, _dptr(z), _dptr(y)))
+        return y
+
+    __matmul__ = __mul__
+
+    def transpose(self):  # the composite is symmetric and real
+        return self
+
+    T = property(transpose)
+    ctranspose = transpose
+    H = property(transpose)
+    conj = transpose
+
+    def to_dense(self, chunk=64):
+        """double(op) = op * eye(n), `chunk` columns at a time (device memory O(N * chunk))."""
+        X = np.empty((self.n, self.n), order="F")
+        for j0 in range(0, self.n, chunk):
+            j1 = min(self.n, j0 + chunk)
+            E = np.zeros((self.n, j1 - j0), order="F")
+            E[np.arange(j0, j1), np.arange(j1 - j0)] = 1.0
+            X[:, j0:j1] = self @ E
+        return X
 
 
 def _options_spec(ctx, options):

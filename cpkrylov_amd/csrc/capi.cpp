@@ -457,6 +457,78 @@ int cpk_pc_apply_device(cpk_pc M, const double *d_x, double *d_y) {
     API_END
 }
 
+// ---- the bare factor composite: opLDL2's M' and conj(M) (opLDL2.m:127-136) ---------------------
+// One LDL solve on the device factors: no refinement, no residual update, none of their state.
+int cpk_pc_apply_ldl(cpk_pc M, const double *x, double *y) {
+    API_BEGIN
+    need(M && x && y, "NULL argument");
+    Precond &p = *M->p;
+    Ctx &c = M->ctx->c;
+    DBuf<double> dx, dy;
+    if (p.dist) scatter_global(p, x, p.N, dx);
+    else h2d(dx, x, (size_t)p.N);
+    dy.alloc((size_t)std::max<int64_t>(p.N, 1));
+    p.ldl_solve(dx.p, p.N, dy.p, false, nullptr, nullptr);
+    if (p.dist) {
+        gather_global(c, p, dy.p, y);
+    } else {
+        CPK_HIP(hipMemcpyAsync(y, dy.p, p.N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+    }
+    check_chain(p.dF);
+    check_chain(p.sep.tsw);
+    API_END
+}
+
+int cpk_pc_apply_ldl_device(cpk_pc M, const double *d_x, double *d_y) {
+    API_BEGIN
+    need(M && d_x && d_y, "NULL argument");
+    M->p->ldl_solve(d_x, M->p->N, d_y, false, nullptr, nullptr);
+    API_END
+}
+
+static void check_multi(const Precond &p, int64_t k, int64_t ldx, int64_t ldy) {
+    if (k < 0 || ldx < p.gN || ldy < p.gN)
+        throw Error(CPK_ERR_DIM, "apply_ldl_multi: k >= 0 and leading dimensions >= N required");
+    if (p.dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column factor apply: single-GPU only");
+}
+
+int cpk_pc_apply_ldl_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy) {
+    API_BEGIN
+    need(M && d_X && d_Y, "NULL argument");
+    check_multi(*M->p, k, ldx, ldy);
+    M->p->ldl_solve_multi(k, d_X, ldx, d_Y, ldy);
+    API_END
+}
+
+int cpk_pc_apply_ldl_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    API_BEGIN
+    need(M && X && Y, "NULL argument");
+    Precond &p = *M->p;
+    Ctx &c = M->ctx->c;
+    check_multi(p, k, ldx, ldy);
+    if (k == 0 || p.N == 0) return CPK_OK;
+    // packed on the device (leading dimension N); the caller's padding rows are never touched
+    const size_t rowb = (size_t)p.N * sizeof(double);
+    DBuf<double> dX, dY;
+    dX.alloc((size_t)p.N * (size_t)k), dY.alloc((size_t)p.N * (size_t)k);
+    CPK_HIP(hipMemcpy2D(dX.p, rowb, X, (size_t)ldx * sizeof(double), rowb, (size_t)k, hipMemcpyHostToDevice));
+    p.ldl_solve_multi(k, dX.p, p.N, dY.p, p.N);
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, rowb, rowb, (size_t)k, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int cpk_pc_multi_info(cpk_pc M, int64_t *info) {
+    API_BEGIN
+    need(M && info, "NULL argument");
+    if (M->p->dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column factor apply: single-GPU only");
+    const MultiPlan &mp = multisweep_plan(M->p->dF);
+    const int64_t v[4] = {kMultiKP, mp.launches, mp.staged, mp.direct};
+    std::memcpy(info, v, sizeof v);
+    API_END
+}
+
 int cpk_pc_divide(cpk_pc M, const double *b, double *x) {
     API_BEGIN
     need(M && b && x, "NULL argument");

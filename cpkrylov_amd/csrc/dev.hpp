@@ -235,6 +235,15 @@ struct DChain {
     DBuf<uint32_t> flag, ctrl;
 };
 
+// The multi-column sweep's launch plan of a factor (multisweep.hip): lds[2 r + bwd] = dynamic LDS of
+// round r's launch (its largest staged block's image), and the path counts of cpk_pc_multi_info
+constexpr int kMultiKP = 8;  // columns per panel
+struct MultiPlan {
+    bool ready = false;
+    std::vector<size_t> lds;
+    int64_t launches = 0, staged = 0, direct = 0;
+};
+
 // HBM-resident factor + sweep schedule (rows in schedule order).
 struct DFactor {
     int64_t N = 0, nnz = 0, nblk = 0, nlvl = 0;
@@ -278,6 +287,7 @@ struct DFactor {
     std::vector<int64_t> hmodel; // the upper blocks' loop-cost model (mark_dataflow; diagnostic)
     // (first, last) block of a launch -> its blocks' largest rows / entries (the LDS image, kernels.hip)
     mutable std::map<std::pair<int64_t, int64_t>, std::pair<int, int>> img_cache;
+    mutable MultiPlan multi;  // built on first use (multisweep_plan)
     // round-0 blocks assigned to the persistent launch's workgroups by modelled cost (plan_round0),
     // per kernel variant v (0 forward, 1 forward with the fused refinement residual, 2 backward):
     // workgroup g runs the BlkMeta records ameta[v][aptr[v][g] .. aptr[v][g + 1]); agrid[v] = the
@@ -391,6 +401,13 @@ void launch_spmv_resid_sched(Ctx &c, const DMat &A, const int32_t *perm, const d
 bool launch_sptrsv_fwd_resid(Ctx &c, const DFactor &F, const DMat &Kps, const double *xs, const double *y, double *r,
                              const int *run, FwdIn *defer = nullptr, const PackArgs *pk = nullptr,
                              bool *packed = nullptr);
+// ---- multi-column sweep (multisweep.hip) --------------------------------------------------
+// Y(:, j) = P * (L' \ (D \ (L \ P' * X(:, j)))) for j < k, column-major with leading dimensions
+// ldx, ldy >= N, in panels of kMultiKP columns through `panel` (N * kMultiKP doubles, rows in
+// schedule order).  Single GPU.  Each column equals the single-column sweeps' result bit for bit.
+const MultiPlan &multisweep_plan(const DFactor &F);
+void launch_multisweep(Ctx &c, const DFactor &F, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       double *panel);
 // buf[slot[q]] = w[q] for q < n with slot[q] >= 0 (a payload the sweeps' write-back did not pack)
 void launch_pack_slots(Ctx &c, const int32_t *slot, int64_t n, const double *w, double *buf, const int *run);
 int debug_pipe_stamps(uint64_t *out, int npairs);  // diagnostic build only (CPK_PIPE_STAMPS)
@@ -561,6 +578,7 @@ struct Precond {
     DMat dKp;
     DFactor dF;
     DBuf<double> w, r;   // permuted work vector, refinement residual
+    DBuf<double> panel;  // the multi-column sweep's work array (N * kMultiKP), allocated on first use
     DLdl dl;             // device numeric factorization (single GPU); dl.ready: F.Lx / F.D live on the device
     // single GPU, forced refinement: Kp permuted into schedule order (P'*Kp*P, each row's
     // entries in Kp's order) so the refinement residual, the forward sweep's input and the
@@ -612,6 +630,9 @@ struct Precond {
     // residual is formed after the exchange); 0 neither
     bool ldl_solve(const double *xin, int64_t neg_from, double *y, bool add, const int *run, const int *act,
                    const double *piggy_src = nullptr, int stage = 0, const double *xT = nullptr, int64_t xT_neg = 0);
+    // Y = LDL * X for k columns (device, column-major): the bare composite, no refinement and no
+    // residual-update state; single GPU (CPK_ERR_UNSUPPORTED on a distributed preconditioner)
+    void ldl_solve_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
     DBuf<int32_t> hslot;  // distributed: local output index -> Kp halo slot (-1: none); empty: no packing
     // distributed, one forced refinement step: the residual without the Kp halo exchange
     // (DESIGN.md section 7).  Kp couples a subtree row only with its own subtree and with T, and

@@ -793,6 +793,15 @@ bool Precond::ldl_solve(const double *xin, int64_t neg_from, double *y, bool add
     return launch_sptrsv_bwd(c, dF, w.p, y, add, run, act, nullptr, nullptr, (hpack || stage == 1) ? &bp : nullptr);
 }
 
+// Y = LDL * X, k columns in panels (multisweep.hip): L is streamed once per panel instead of
+// once per column; the panel buffer is not part of the factor (DFactor::bytes)
+void Precond::ldl_solve_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    if (dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column factor apply: single-GPU only");
+    if (k <= 0 || N <= 0) return;
+    if (panel.n < (size_t)N * kMultiKP) panel.alloc((size_t)N * kMultiKP);
+    launch_multisweep(*ctx, dF, k, X, ldx, Y, ldy, panel.p);
+}
+
 // the forward sweep's separator payload: its rows' values by tslot, rank 0's T inputs +-xt[tdof]
 // and the piggyback values (tpack_kernel's work, in the write-back)
 PackArgs Precond::fwd_pack(const double *xt, int64_t xt_neg, const double *piggy_src) const {

@@ -204,6 +204,25 @@ int cpk_pc_set_handle(cpk_pc M, int on);
 int cpk_pc_apply(cpk_pc M, const double *x, double *y);
 /* Same on device pointers, enqueued on the context stream. */
 int cpk_pc_apply_device(cpk_pc M, const double *d_x, double *d_y);
+/* y = M'*x = conj(M)*x: the bare factor composite P*L'^-1*D^-1*L^-1*P' (opLDL2.m:127-136), one
+ * LDL solve on the device factors.  Unlike cpk_pc_apply it runs no refinement and no residual
+ * update: nitref, itref_tol, force_itref, residual_update and the handle-mode state are neither
+ * read nor written.  Host vectors of length N (global on a distributed preconditioner). */
+int cpk_pc_apply_ldl(cpk_pc M, const double *x, double *y);
+/* Same on device pointers (a distributed preconditioner: the rank's local slice). */
+int cpk_pc_apply_ldl_device(cpk_pc M, const double *d_x, double *d_y);
+/* Y = M'*X for a block of k right-hand sides (the reference's M' * X with an N x k matrix):
+ * column-major, column j at X + j*ldx and Y + j*ldy, ldx, ldy >= N and k >= 0 (CPK_ERR_DIM
+ * otherwise; k == 0 does nothing).  X and Y must not overlap (not checked).  The columns are
+ * solved in panels of 8 by a sweep that streams L once per panel; column j of Y equals
+ * cpk_pc_apply_ldl on column j of X bit for bit.  Rows [N, ldy) of Y are not touched.  Single GPU
+ * (CPK_ERR_UNSUPPORTED on a distributed preconditioner). */
+int cpk_pc_apply_ldl_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
+int cpk_pc_apply_ldl_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy);
+/* Diagnostic (not in the reference): the multi-column sweep as the preconditioner's last or next
+ * panel solve runs it, info[4] = {columns per panel, kernel launches per panel solve, blocks
+ * staged in LDS, blocks on the direct path through global memory} (multi-column sweep). */
+int cpk_pc_multi_info(cpk_pc M, int64_t *info);
 /* x = Kp*b (opLDL2.divide, opLDL2.m:193-195). */
 int cpk_pc_divide(cpk_pc M, const double *b, double *x);
 int cpk_pc_get_info(cpk_pc M, cpk_pc_info *info);

@@ -8,6 +8,8 @@
  *   h = cpk_mex('pc_create', G, B, Cneg)        % opLDL2(G, B, Cneg)       (opLDL2.m:60-92)
  *       cpk_mex('pc_set', h, opts)              % M.nitref = ... etc.      (opLDL2.m:97-115)
  *   y = cpk_mex('pc_apply', h, x)               % y = M*x                  (opLDL2.m:161-188)
+ *   Y = cpk_mex('pc_apply_ldl', h, X)           % Y = M'*X = conj(M)*X, X dense N x k: the bare
+ *                                               % factor composite         (opLDL2.m:127-136)
  *   x = cpk_mex('pc_divide', h, b)              % x = Kp*b                 (opLDL2.m:193-195)
  *       cpk_mex('pc_destroy', h)
  *   [x, y, stats, flag] = cpk_mex('method', name, b, A, C, h, opts)
@@ -178,7 +180,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     mxGetString(prhs[0], cmd, sizeof cmd);
     {   /* argument counts before anything is converted or a device is touched */
         static const struct { const char *cmd; int nrhs; } need[] = {
-            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
+            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
             {"method", 6}, {"reg_solve", 7}};
         int i;
         for (i = 0; i < (int)(sizeof need / sizeof need[0]); i++)
@@ -200,6 +202,20 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         cpk_pc M = to_pc(ARG(1));
         to_opts(ARG(2), &o);
         if ((st = cpk_pc_set(M, &o))) fail(st);
+    } else if (!strcmp(cmd, "pc_apply_ldl")) {
+        cpk_pc M = to_pc(ARG(1));
+        cpk_pc_info info;
+        int64_t k;
+        if ((st = cpk_pc_get_info(M, &info))) fail(st);
+        if (!ARG(2) || mxIsSparse(ARG(2)) || mxIsComplex(ARG(2)) || (int64_t)mxGetM(ARG(2)) != info.N)
+            fail_msg("cpk:dim", "expected a dense real matrix with %lld rows", (long long)info.N);
+        k = (int64_t)mxGetN(ARG(2));
+        plhs[0] = mxCreateDoubleMatrix((mwSize)info.N, (mwSize)k, mxREAL);
+        if (k == 1)
+            st = cpk_pc_apply_ldl(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]));
+        else if (k > 0 && info.N > 0) /* MATLAB stores a dense matrix column-major, leading dimension N */
+            st = cpk_pc_apply_ldl_multi(M, k, mxGetPr(ARG(2)), info.N, mxGetPr(plhs[0]), info.N);
+        if (st) fail(st);
     } else if (!strcmp(cmd, "pc_apply") || !strcmp(cmd, "pc_divide")) {
         cpk_pc M = to_pc(ARG(1));
         cpk_pc_info info;

@@ -56,14 +56,16 @@ classdef opCpkLDL2 < opSpot
       function opOut = transpose(op)
          opOut = op;
       end
-      % conj / ctranspose (opLDL2.m:127-137): P*inv(conj(L)')*inv(conj(D))*inv(conj(L))*P'.  The
-      % factors are real (complex systems are out of scope, opLDL2.m:80's cflag), so conj of the
-      % operator is the operator and its conjugate transpose is its transpose: itself
+      % conj / ctranspose (opLDL2.m:127-136): not the operator itself but the bare factor
+      % composite P*inv(L')*inv(D)*inv(L)*P' -- one LDL solve without refinement or residual
+      % update, whatever the properties say -- and, unlike M, applicable to a block M' * X.
+      % The factors are real (complex systems are out of scope, opLDL2.m:80's cflag), so the two
+      % coincide; opCpkLDLFactor applies them on the same device factorization
       function opOut = conj(op)
-         opOut = op;
+         opOut = opCpkLDLFactor(op.h, op.nA + op.nC);
       end
       function opOut = ctranspose(op)
-         opOut = op;
+         opOut = opCpkLDLFactor(op.h, op.nA + op.nC);
       end
       % double (opLDL2.m:138-149): the dense matrix, one column op * e_i at a time -- the same
       % products the reference forms (each a device apply with the current properties)
