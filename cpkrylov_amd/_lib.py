@@ -77,6 +77,8 @@ _SIGS = {
     "cpk_pc_apply_ldl_multi": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64], C.c_int),
     "cpk_pc_apply_ldl_multi_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64], C.c_int),
     "cpk_pc_multi_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_pc_apply_multi": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_int32)], C.c_int),
+    "cpk_pc_apply_multi_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp], C.c_int),
     "cpk_pc_divide": ([vp, P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_pc_get_info": ([vp, P(PcInfo)], C.c_int),
     "cpk_pc_export": ([vp, P(C.c_int64), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_int32)], C.c_int),

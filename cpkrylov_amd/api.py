@@ -218,6 +218,9 @@ class opLDL2:
       itref_tol       stored as given (the reference's `sef.itref_tol` typo) (default 1e-8)
       force_itref     anything other than false/true becomes false (default false)
       residual_update stored as given (default false); a functional no-op, as in the reference
+
+    `M * z` / `M @ z` with a vector (or an N x 1 array) is opLDL2.multiply; with an N x k array,
+    k != 1, it is the block apply `apply_block`: M on every column, bit for bit.
     """
 
     def __init__(self, A, B, Cm, ctx=None, _handle=None, krylov_A=None):
@@ -280,7 +283,10 @@ class opLDL2:
 
     # ---- operator surface --------------------------------------------------------------------
     def __mul__(self, z):
-        z = np.ascontiguousarray(z, dtype=np.float64).ravel()
+        z = np.asarray(z, dtype=np.float64)
+        if z.ndim == 2 and z.shape[1] != 1:  # a block: M*Z column by column (apply_block)
+            return self.apply_block(z)
+        z = np.ascontiguousarray(z).ravel()
         if z.shape[0] != self.n:
             raise CpkError(_lib.CPK_ERR_DIM, "Dimensions do not match")
         y = np.empty(self.n)
@@ -288,6 +294,25 @@ class opLDL2:
         return y
 
     __matmul__ = __mul__
+
+    def apply_block(self, Z, return_steps=False):
+        """Y = M*Z for an N x k array (any memory order), defined column by column: Y[:, j] equals
+        `M * Z[:, j]` bit for bit under the current nitref / itref_tol / force_itref, each column
+        with its own refinement predicate (cpk_pc_apply_multi: panels of 8 columns stream the
+        factor and Kp once per panel).  return_steps: also the refinement solves each column
+        took (int32, 0...nitref).  The reference's matrix path (norm(r) over the whole block) is
+        not reproduced."""
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[0] != self.n:
+            raise CpkError(_lib.CPK_ERR_DIM, "Dimensions do not match")
+        k = Z.shape[1]
+        X = np.asfortranarray(Z)
+        Y = np.empty((self.n, k), order="F")
+        nit = np.zeros(k, np.int32)
+        if k:
+            check(lib.cpk_pc_apply_multi(self.h, k, _dptr(X), max(self.n, 1), _dptr(Y), max(self.n, 1),
+                                         nit.ctypes.data_as(_P(C.c_int32))))
+        return (Y, nit) if return_steps else Y
 
     def divide(self, b):
         """M \\ b = Kp*b  (opLDL2.divide, opLDL2.m:193-195)."""
@@ -313,13 +338,23 @@ class opLDL2:
         check(lib.cpk_pc_multi_info(self.h, v))
         return dict(zip(("kp", "launches", "staged_blocks", "direct_blocks"), list(v)))
 
-    def to_dense(self):  # double(op), opLDL2.m:138-149
-        e = np.zeros(self.n)
-        X = np.zeros((self.n, self.n))
-        for i in range(self.n):
-            e[i] = 1
-            X[:, i] = self * e
-            e[i] = 0
+    def to_dense(self, chunk=64):
+        """double(op), opLDL2.m:138-149: one op*e per column, `chunk` columns per block apply
+        (device memory O(N * chunk)); bit-equal to the loop of `self * e_j`."""
+        X = np.empty((self.n, self.n), order="F")
+        if self.ctx.info()["distributed"] or (self.handle_semantics and self.residual_update):
+            # the block entry is single-GPU and keeps no residual-update state: one apply per column
+            e = np.zeros(self.n)
+            for i in range(self.n):
+                e[i] = 1
+                X[:, i] = self * e
+                e[i] = 0
+            return X
+        for j0 in range(0, self.n, chunk):
+            j1 = min(self.n, j0 + chunk)
+            E = np.zeros((self.n, j1 - j0), order="F")
+            E[np.arange(j0, j1), np.arange(j1 - j0)] = 1.0
+            X[:, j0:j1] = self.apply_block(E)
         return X
 
     def sep_info(self):
@@ -366,7 +401,7 @@ class opLDL2:
 class opLDL2Factor:
     """M' and conj(M) of an opLDL2: the bare factor composite P*L'^-1*D^-1*L^-1*P'
     (opLDL2.m:127-136), applied once -- no refinement, no residual update, none of M's properties
-    read or written.  It shares M's handle and keeps M alive.  Unlike M it takes a block of
+    read or written.  It shares M's handle and keeps M alive.  It takes a block of
     right-hand sides: `F @ X` with an N x k array solves the k columns in panels, streaming the
     factor once per panel (cpk_pc_apply_ldl_multi); each column equals `F * X[:, j]` bit for bit."""
 

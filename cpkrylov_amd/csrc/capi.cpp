@@ -519,6 +519,53 @@ int cpk_pc_apply_ldl_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, do
     API_END
 }
 
+// ---- the refined apply for a block: Y(:, j) = M * X(:, j), opLDL2.multiply per column -----------
+// the checks of cpk_pc_apply_ldl_multi, and X and Y may not overlap (Y is written while X is
+// still read by the refinement residuals)
+static void check_apply_multi(const Precond &p, int64_t k, const double *X, int64_t ldx, const double *Y, int64_t ldy) {
+    if (k < 0 || ldx < p.gN || ldy < p.gN)
+        throw Error(CPK_ERR_DIM, "apply_multi: k >= 0 and leading dimensions >= N required");
+    if (p.dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: single-GPU only");
+    if (p.residual_update != 0 && p.handle)
+        throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: the handle semantics of residual_update keep one state vector");
+    if (k == 0 || p.N == 0) return;
+    const uintptr_t x0 = (uintptr_t)X, y0 = (uintptr_t)Y;
+    const uintptr_t x1 = x0 + ((size_t)(k - 1) * (size_t)ldx + (size_t)p.N) * sizeof(double);
+    const uintptr_t y1 = y0 + ((size_t)(k - 1) * (size_t)ldy + (size_t)p.N) * sizeof(double);
+    if (x0 < y1 && y0 < x1) throw Error(CPK_ERR_ARGS, "apply_multi: X and Y overlap");
+}
+
+int cpk_pc_apply_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
+                              int32_t *d_nit) {
+    API_BEGIN
+    need(M && d_X && d_Y, "NULL argument");
+    check_apply_multi(*M->p, k, d_X, ldx, d_Y, ldy);
+    M->p->apply_multi(k, d_X, ldx, d_Y, ldy, d_nit);
+    API_END
+}
+
+int cpk_pc_apply_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit) {
+    API_BEGIN
+    need(M && X && Y, "NULL argument");
+    Precond &p = *M->p;
+    Ctx &c = M->ctx->c;
+    check_apply_multi(p, k, X, ldx, Y, ldy);
+    if (k == 0 || p.N == 0) return CPK_OK;
+    // packed on the device (leading dimension N); the caller's padding rows are never touched
+    const size_t rowb = (size_t)p.N * sizeof(double);
+    DBuf<double> dX, dY;
+    DBuf<int32_t> dn;
+    dX.alloc((size_t)p.N * (size_t)k), dY.alloc((size_t)p.N * (size_t)k);
+    if (nit) dn.alloc((size_t)k);
+    CPK_HIP(hipMemcpy2D(dX.p, rowb, X, (size_t)ldx * sizeof(double), rowb, (size_t)k, hipMemcpyHostToDevice));
+    p.apply_multi(k, dX.p, p.N, dY.p, p.N, dn.p);
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    check_chain(p.dF);
+    CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, rowb, rowb, (size_t)k, hipMemcpyDeviceToHost));
+    if (nit) CPK_HIP(hipMemcpy(nit, dn.p, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    API_END
+}
+
 int cpk_pc_multi_info(cpk_pc M, int64_t *info) {
     API_BEGIN
     need(M && info, "NULL argument");

@@ -135,6 +135,8 @@ struct EngineOpts {
     bool dist_graph = true;       // dist_graph:         capture collectives in the graphs
     bool dist1 = false;           // dist1:              a 1-rank communicator runs the distributed path
                                   //                     (diagnostic; set before building operators)
+    bool apply_multi_panel = false;  // apply_multi_panel: the refined block apply always on the panel kernels
+                                  //                     (else panels below the break-even loop over columns)
     bool exact_dots = false;      // exact_dots:         every inner product the correctly rounded exact sum
                                   //                     of its TwoProd pairs (xacc.hpp): order-independent,
                                   //                     the oracle's orc_set_exact values bit for bit; the
@@ -238,6 +240,11 @@ struct DChain {
 // The multi-column sweep's launch plan of a factor (multisweep.hip): lds[2 r + bwd] = dynamic LDS of
 // round r's launch (its largest staged block's image), and the path counts of cpk_pc_multi_info
 constexpr int kMultiKP = 8;  // columns per panel
+// the refined block apply (Precond::apply_multi) runs a panel of fewer columns than this as a
+// loop of single-column applies: the measured break-even (profiles/apply_multi_timing.json,
+// DESIGN.md "Refined block apply": at S10 +-4 a panel of 6 columns still loses to six
+// single-column applies, 9.70 against 9.03 ms, a panel of 7 wins, 9.79 against 10.53 ms)
+constexpr int kApplyMultiMinCols = 7;
 struct MultiPlan {
     bool ready = false;
     std::vector<size_t> lds;
@@ -408,6 +415,34 @@ bool launch_sptrsv_fwd_resid(Ctx &c, const DFactor &F, const DMat &Kps, const do
 const MultiPlan &multisweep_plan(const DFactor &F);
 void launch_multisweep(Ctx &c, const DFactor &F, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
                        double *panel);
+// ---- refined block apply (multisweep.hip, multiapply.hip) ---------------------------------
+// One panel of kc <= kMultiKP columns of Y = M*X.  Yp / Rp: the natural-order solution and
+// residual panels, [i * kMultiKP + j].  state (device): MultiState.
+struct MultiState {
+    int32_t act[kMultiKP];  // column j still refines
+    int32_t any;            // any column of the panel does
+    int32_t nit[kMultiKP];  // refinement solves column j took
+};
+// Yp = LDL * X (every column of the panel; the padding columns are zeros)
+void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel);
+// Yp(:, j) += LDL * Rp(:, j) for the columns with act[j] != 0 (the others are not touched); a
+// panel with any == 0 leaves at once
+void launch_multisweep_refine(Ctx &c, const DFactor &F, const double *Rp, double *Yp, const int32_t *act, double *panel);
+void launch_multi_state(Ctx &c, int32_t *state, int kc, int steps);
+// Rp = X - A*Yp, each row summed in spmv_stream's order; norms: part[b][2 * kMultiKP] = row block
+// b's sums of r^2 per column and, with first, of x^2 per column
+void launch_multi_resid(Ctx &c, const DMat &A, int kc, const double *X, int64_t ldx, const double *Yp, double *Rp,
+                        const int32_t *state, double *part, bool norms, bool first);
+// act[j] &= ||r_j|| >= tol * ||x_j|| from part summed in block order; nit[j] = step + 1 where it
+// holds; xn2: the columns' sums of x^2 (written with first, read afterwards)
+void launch_multi_pred(Ctx &c, const double *part, int64_t nblk, double tol, int step, bool first, int32_t *state,
+                       double *xn2);
+// Y(0:N, j) = Yp(:, j) for j < kc, nit[j] = the state's count (nit may be null)
+void launch_multi_store(Ctx &c, int64_t N, int kc, const double *Yp, double *Y, int64_t ldy, const int32_t *state,
+                        int32_t *nit);
+// the single-column apply's step count: *nit = v; *nit += (*active != 0)
+void launch_nit_set(Ctx &c, int32_t *nit, int v);
+void launch_nit_count(Ctx &c, int32_t *nit, const int *active);
 // buf[slot[q]] = w[q] for q < n with slot[q] >= 0 (a payload the sweeps' write-back did not pack)
 void launch_pack_slots(Ctx &c, const int32_t *slot, int64_t n, const double *w, double *buf, const int *run);
 int debug_pipe_stamps(uint64_t *out, int npairs);  // diagnostic build only (CPK_PIPE_STAMPS)
@@ -618,7 +653,10 @@ struct Precond {
     // piggy_src (distributed only, piggyback_ok()): kSepPiggy device values appended to the first
     // separator exchange's payload, e.g. a solver's deferred inner-product partials; after the
     // apply every rank finds rank r's values at sep.rbuf[r * sep.kt + sep.kt_data + j]
-    void apply(const double *x, int64_t neg_from, double *y, const int *run, const double *piggy_src = nullptr);
+    // nit (optional, device): receives the refinement solves taken, 0...nitref (two tiny launches
+    // more; the block apply's column loop asks for it)
+    void apply(const double *x, int64_t neg_from, double *y, const int *run, const double *piggy_src = nullptr,
+               int32_t *nit = nullptr);
     bool piggyback_ok() const { return dist && sep.kt > 0; }
     // the schedule-order refinement path (single GPU; CPK_NO_SCHED_RESID=1 forces the plain one)
     bool sched_path() const { return !dist && dKps.nnz > 0 && !no_sched; }
@@ -633,6 +671,19 @@ struct Precond {
     // Y = LDL * X for k columns (device, column-major): the bare composite, no refinement and no
     // residual-update state; single GPU (CPK_ERR_UNSUPPORTED on a distributed preconditioner)
     void ldl_solve_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
+    // Y = M * X for k columns (device, column-major): column j is apply() on column j bit for bit,
+    // under the current nitref / itref_tol / force_itref; nit (optional, device): k step counts.
+    // Panels of kMultiKP columns through the panel kernels (multisweep.hip, multiapply.hip), the
+    // predicate per column on the device; a panel of fewer than kApplyMultiMinCols columns runs
+    // as a loop of apply() unless multi_panel (engine option apply_multi_panel) forces the panel
+    // kernels.  Single GPU; CPK_ERR_UNSUPPORTED with the handle semantics of residual_update.
+    void apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit);
+    bool multi_panel = false;
+    // the block apply's work arrays, allocated on first use (not part of DFactor::bytes): the
+    // natural-order solution and residual panels, the row blocks' norm partials, the columns'
+    // sums of x^2 and the panel's MultiState
+    DBuf<double> ypanel, rpanel, mpart, mxn2;
+    DBuf<int32_t> mstate;
     DBuf<int32_t> hslot;  // distributed: local output index -> Kp halo slot (-1: none); empty: no packing
     // distributed, one forced refinement step: the residual without the Kp halo exchange
     // (DESIGN.md section 7).  Kp couples a subtree row only with its own subtree and with T, and

@@ -51,14 +51,29 @@ __host__ __device__ inline bool multi_staged(int nr, int nef, int neb, int R, in
 // never stored).  ptr / col / val: the sweep's rows (forward: fptr..., backward: bptr...), optr:
 // the other direction's row pointers (the staging predicate).  BWD: store_w = 0 skips the panel
 // write-back of staged blocks (round 0: nothing reads it afterwards).
-template <bool BWD>
+// MODE 1: act[j] != 0 marks column j active, act[KP] any of them (null: all active)
+struct MultiRef {
+    const double *Rp = nullptr;    // forward input, natural order
+    double *Yp = nullptr;          // backward output, natural order
+    const int32_t *act = nullptr;  // [KP + 1] on the device
+    int acc = 0;                   // backward: Yp += w for the active columns (0: Yp = w, every column)
+};
+
+template <bool BWD, int MODE>
 __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
     int64_t blk0, int R, int CAP, int lds_limit, const int32_t *__restrict__ blk_lvl, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ optr, const int32_t *__restrict__ col,
     const double *__restrict__ val, const double *__restrict__ D, const int32_t *__restrict__ perm,
-    const double *__restrict__ X, int64_t ldx, double *__restrict__ Y, int64_t ldy, int kc, double *W, int store_w) {
+    const double *__restrict__ X, int64_t ldx, double *__restrict__ Y, int64_t ldy, int kc, double *W, int store_w,
+    MultiRef ref) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TPB = kMultiThreads;
+    static_assert(TPB % KP == 0, "a thread keeps its column across strided passes");
+    bool on = true;  // MODE 1: this thread's column (threadIdx.x % KP) is active
+    if (MODE == 1 && ref.act) {
+        if (ref.act[KP] == 0) return;
+        on = ref.act[threadIdx.x % KP] != 0;
+    }
     const int64_t b = blk0 + blockIdx.x;
     const int l0 = blk_lvl[b], l1 = blk_lvl[b + 1];
     const int r0 = lvl_row[l0], r1 = lvl_row[l1];
@@ -77,6 +92,9 @@ __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
         __syncthreads();
         if (BWD) {
             for (int i = tid; i < nr * KP; i += TPB) Wl[i] = W[(size_t)r0 * KP + i] / D[r0 + i / KP];
+        } else if (MODE == 1) {
+            for (int i = tid; i < nr * KP; i += TPB)  // one 64-byte segment per row; i % KP == tid % KP
+                Wl[i] = on ? ref.Rp[(size_t)perm[r0 + i / KP] * KP + i % KP] : 0.0;
         } else {
             // gather with the row fastest across lanes, as the single-column sweep reads x(perm)
             for (int i = tid; i < nr * KP; i += TPB) {
@@ -152,11 +170,18 @@ __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
         }
         if (!BWD || store_w)
             for (int i = tid; i < nr * KP; i += TPB) W[(size_t)r0 * KP + i] = Wl[i];
-        if (BWD)
+        if (BWD && MODE == 1) {
+            for (int i = tid; i < nr * KP; i += TPB) {
+                double *y = ref.Yp + (size_t)perm[r0 + i / KP] * KP + i % KP;
+                if (!ref.acc) *y = Wl[i];
+                else if (on) *y = *y + Wl[i];
+            }
+        } else if (BWD) {
             for (int i = tid; i < nr * kc; i += TPB) {
                 const int j = i / nr, row = i - j * nr;
                 Y[(int64_t)perm[r0 + row] + (int64_t)j * ldy] = Wl[row * KP + j];
             }
+        }
         return;
     }
     // direct path through global memory: a block above the configured shape (a factor row longer
@@ -168,11 +193,18 @@ __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
             const int k = a + (int)(i / KP), j = (int)(i % KP);
             double acc;
             if (BWD) acc = W[(size_t)k * KP + j] / D[k];
+            else if (MODE == 1) acc = on ? ref.Rp[(size_t)perm[k] * KP + j] : 0.0;
             else acc = j < kc ? X[(int64_t)perm[k] + (int64_t)j * ldx] : 0.0;
             const uint32_t q1 = ptr[k + 1];
             for (uint32_t e = ptr[k]; e < q1; e++) acc -= val[e] * W[(size_t)col[e] * KP + j];
             W[(size_t)k * KP + j] = acc;
-            if (BWD && j < kc) Y[(int64_t)perm[k] + (int64_t)j * ldy] = acc;
+            if (BWD && MODE == 1) {
+                double *y = ref.Yp + (size_t)perm[k] * KP + j;
+                if (!ref.acc) *y = acc;
+                else if (on) *y = *y + acc;
+            } else if (BWD && j < kc) {
+                Y[(int64_t)perm[k] + (int64_t)j * ldy] = acc;
+            }
         }
         __syncthreads();
     }
@@ -182,10 +214,10 @@ __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
 // kernels the opt-in (asked once)
 int multi_lds_limit() {
     static const int limit = [] {
-        const bool ok = hipFuncSetAttribute((const void *)multisweep_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)kMultiMaxLds) == hipSuccess &&
-                        hipFuncSetAttribute((const void *)multisweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)kMultiMaxLds) == hipSuccess;
+        bool ok = true;
+        for (const void *f : {(const void *)multisweep_kernel<false, 0>, (const void *)multisweep_kernel<true, 0>,
+                              (const void *)multisweep_kernel<false, 1>, (const void *)multisweep_kernel<true, 1>})
+            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMultiMaxLds) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();  // not granted: no error left behind for the launches' check
         return ok ? (int)kMultiMaxLds : 64 * 1024;
     }();
@@ -223,34 +255,67 @@ const MultiPlan &multisweep_plan(const DFactor &F) {
     return p;
 }
 
-void launch_multisweep(Ctx &c, const DFactor &F, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
-                       double *panel) {
+namespace {
+
+// one panel's forward rounds (ascending) / backward rounds (descending), one launch per round
+template <int MODE>
+void multi_fwd_rounds(Ctx &c, const DFactor &F, const double *Xp, int64_t ldx, int kc, double *panel, const MultiRef &ref) {
     const MultiPlan &p = multisweep_plan(F);
     const int64_t R = (int64_t)F.round_ptr.size() - 1;
     const int limit = multi_lds_limit();
+    for (int64_t r = 0; r < R; r++) {
+        const int i = r == 0 ? 0 : 1;
+        const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
+        if (!nb) continue;
+        hipLaunchKernelGGL((multisweep_kernel<false, MODE>), dim3((unsigned)nb), dim3(kMultiThreads), p.lds[(size_t)r * 2],
+                           c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p, F.lvl_row.p, F.fptr.p,
+                           F.bptr.p, F.fcol.p, F.fval.p, F.D.p, F.perm.p, Xp, ldx, (double *)nullptr, (int64_t)0, kc, panel,
+                           1, ref);
+    }
+}
+
+template <int MODE>
+void multi_bwd_rounds(Ctx &c, const DFactor &F, double *Yp, int64_t ldy, int kc, double *panel, const MultiRef &ref) {
+    const MultiPlan &p = multisweep_plan(F);
+    const int64_t R = (int64_t)F.round_ptr.size() - 1;
+    const int limit = multi_lds_limit();
+    for (int64_t r = R - 1; r >= 0; r--) {
+        const int i = r == 0 ? 0 : 1;
+        const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
+        if (!nb) continue;
+        // the backward sweep's last round: nothing reads its staged blocks' panel rows again
+        hipLaunchKernelGGL((multisweep_kernel<true, MODE>), dim3((unsigned)nb), dim3(kMultiThreads),
+                           p.lds[(size_t)r * 2 + 1], c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p,
+                           F.lvl_row.p, F.bptr.p, F.fptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p, (const double *)nullptr,
+                           (int64_t)0, Yp, ldy, kc, panel, r == 0 ? 0 : 1, ref);
+    }
+}
+
+}  // namespace
+
+void launch_multisweep(Ctx &c, const DFactor &F, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       double *panel) {
     for (int64_t j0 = 0; j0 < k; j0 += KP) {
         const int kc = (int)std::min<int64_t>(KP, k - j0);
-        const double *Xp = X + j0 * ldx;
-        double *Yp = Y + j0 * ldy;
-        for (int64_t r = 0; r < R; r++) {
-            const int i = r == 0 ? 0 : 1;
-            const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
-            if (!nb) continue;
-            hipLaunchKernelGGL((multisweep_kernel<false>), dim3((unsigned)nb), dim3(kMultiThreads), p.lds[(size_t)r * 2],
-                               c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p, F.lvl_row.p, F.fptr.p,
-                               F.bptr.p, F.fcol.p, F.fval.p, F.D.p, F.perm.p, Xp, ldx, Yp, ldy, kc, panel, 1);
-        }
-        for (int64_t r = R - 1; r >= 0; r--) {
-            const int i = r == 0 ? 0 : 1;
-            const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
-            if (!nb) continue;
-            // the backward sweep's last round: nothing reads its staged blocks' panel rows again
-            hipLaunchKernelGGL((multisweep_kernel<true>), dim3((unsigned)nb), dim3(kMultiThreads),
-                               p.lds[(size_t)r * 2 + 1], c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p,
-                               F.lvl_row.p, F.bptr.p, F.fptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p, Xp, ldx, Yp, ldy, kc,
-                               panel, r == 0 ? 0 : 1);
-        }
+        multi_fwd_rounds<0>(c, F, X + j0 * ldx, ldx, kc, panel, MultiRef{});
+        multi_bwd_rounds<0>(c, F, Y + j0 * ldy, ldy, kc, panel, MultiRef{});
     }
+    CPK_HIP(hipGetLastError());
+}
+
+void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel) {
+    MultiRef ref;
+    ref.Yp = Yp;
+    multi_fwd_rounds<0>(c, F, X, ldx, kc, panel, MultiRef{});
+    multi_bwd_rounds<1>(c, F, nullptr, 0, kc, panel, ref);
+    CPK_HIP(hipGetLastError());
+}
+
+void launch_multisweep_refine(Ctx &c, const DFactor &F, const double *Rp, double *Yp, const int32_t *act, double *panel) {
+    MultiRef ref;
+    ref.Rp = Rp, ref.Yp = Yp, ref.act = act, ref.acc = 1;
+    multi_fwd_rounds<1>(c, F, nullptr, 0, KP, panel, ref);
+    multi_bwd_rounds<1>(c, F, nullptr, 0, KP, panel, ref);
     CPK_HIP(hipGetLastError());
 }
 

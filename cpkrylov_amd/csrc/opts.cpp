@@ -75,6 +75,7 @@ const BoolOpt kBool[] = {
     {"exact_dots", &EngineOpts::exact_dots},
     {"no_chain", &EngineOpts::no_chain},
     {"no_bcast_analysis", &EngineOpts::no_bcast_analysis},
+    {"apply_multi_panel", &EngineOpts::apply_multi_panel},
     {"profile_fwd_sched", &EngineOpts::profile_fwd_sched},
     {"profile_passes", &EngineOpts::profile_passes},
 };

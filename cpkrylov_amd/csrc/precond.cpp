@@ -104,6 +104,7 @@ Precond *precond_create(Ctx &c, Analysis &&an, PrecondPre *pre) {
     pc->dF.no_fused_resid = c.opts.no_fused_resid;
     pc->dF.fuse_last = !c.opts.no_fuse_last;  // single GPU: no entries outside the factor
     pc->no_sched = c.opts.no_sched_resid;
+    pc->multi_panel = c.opts.apply_multi_panel;
     // Kp and Kp in schedule order depend only on Kp and the pivot order: they are built and
     // uploaded on a second host thread while this one lays out and uploads the factor
     std::vector<int64_t> kps_ptr;
@@ -802,6 +803,49 @@ void Precond::ldl_solve_multi(int64_t k, const double *X, int64_t ldx, double *Y
     launch_multisweep(*ctx, dF, k, X, ldx, Y, ldy, panel.p);
 }
 
+// Y = M * X column by column (opLDL2.m:174-185 per column), kMultiKP columns at a time:
+//   Yp = LDL*X;  R = X - Kp*Yp;  while a column's predicate holds: Yp += LDL*R, R again.
+// The factor is streamed twice per solve and Kp once per residual for the whole panel.  Nothing
+// here waits for the device: the predicate, the step counts and the panel's "any column active"
+// word live in `mstate`, and every kernel of a panel with no active column leaves at once.
+void Precond::apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit) {
+    if (dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: single-GPU only");
+    if (residual_update != 0 && handle)
+        throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: the handle semantics of residual_update keep one state vector");
+    if (k <= 0 || N <= 0) return;
+    Ctx &c = *ctx;
+    const int steps = nitref > 0 ? (int)std::min<double>(nitref, (double)INT32_MAX) : 0;
+    const bool forced = force_itref != 0;
+    bool ready = false;  // the panel path's work arrays
+    for (int64_t j0 = 0; j0 < k; j0 += kMultiKP) {
+        const int kc = (int)std::min<int64_t>(kMultiKP, k - j0);
+        const double *Xp = X + j0 * ldx;
+        double *Yj = Y + j0 * ldy;
+        int32_t *nj = nit ? nit + j0 : nullptr;
+        if (kc < kApplyMultiMinCols && !multi_panel) {
+            for (int j = 0; j < kc; j++) apply(Xp + j * ldx, N, Yj + j * ldy, nullptr, nullptr, nj ? nj + j : nullptr);
+            continue;
+        }
+        if (!ready) {
+            const size_t pn = (size_t)N * kMultiKP;
+            if (panel.n < pn) panel.alloc(pn);
+            if (ypanel.n < pn) ypanel.alloc(pn), rpanel.alloc(pn);
+            if (mpart.n < (size_t)dKp.nblk * 2 * kMultiKP) mpart.alloc((size_t)dKp.nblk * 2 * kMultiKP);
+            if (!mstate.n) mstate.alloc(sizeof(MultiState) / sizeof(int32_t)), mxn2.alloc(kMultiKP);
+            ready = true;
+        }
+        launch_multi_state(c, mstate.p, kc, forced ? steps : 0);
+        launch_multisweep_first(c, dF, kc, Xp, ldx, ypanel.p, panel.p);
+        for (int s = 0; s < steps; s++) {
+            // forced: the norms are dead; the residual after the last step is never formed
+            launch_multi_resid(c, dKp, kc, Xp, ldx, ypanel.p, rpanel.p, mstate.p, mpart.p, !forced, s == 0);
+            if (!forced) launch_multi_pred(c, mpart.p, dKp.nblk, itref_tol, s, s == 0, mstate.p, mxn2.p);
+            launch_multisweep_refine(c, dF, rpanel.p, ypanel.p, mstate.p, panel.p);
+        }
+        launch_multi_store(c, N, kc, ypanel.p, Yj, ldy, mstate.p, nj);
+    }
+}
+
 // the forward sweep's separator payload: its rows' values by tslot, rank 0's T inputs +-xt[tdof]
 // and the piggyback values (tpack_kernel's work, in the write-back)
 PackArgs Precond::fwd_pack(const double *xt, int64_t xt_neg, const double *piggy_src) const {
@@ -860,8 +904,11 @@ void Precond::set_handle(bool on) {
     }
 }
 
-void Precond::apply(const double *x, int64_t neg_from, double *y, const int *run, const double *piggy_src) {
+void Precond::apply(const double *x, int64_t neg_from, double *y, const int *run, const double *piggy_src,
+                    int32_t *nit) {
     Ctx &c = *ctx;
+    // the step count: every step under force_itref, else one per predicate that held (below)
+    if (nit) launch_nit_set(c, nit, nitref >= 1 && force_itref != 0 ? (int)nitref : 0);
     bool have_xs = false;  // the first forward sweep left the signed x in schedule order (xs)
     bool hpacked = false;  // distributed: y's Kp halo packed by the last backward sweep
     if (residual_update != 0 && handle) {
@@ -923,6 +970,7 @@ void Precond::apply(const double *x, int64_t neg_from, double *y, const int *run
     // data-dependent refinement: the predicate lives on the device, kernels test it
     launch_spmv_resid_norm(c, dKp, x, neg_from, y, r.p, itref_tol, active.p, run, nullptr, hpacked);
     for (int64_t s = 0; s < steps; s++) {
+        if (nit) launch_nit_count(c, nit, active.p);
         // a skipped step (active == 0) leaves y and its packed halo as they were
         hpacked = ldl_solve(r.p, N, y, true, run, active.p);
         if (s + 1 < steps)

@@ -138,6 +138,7 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * no_pipe, no_upper, no_col16, no_dataflow, all_dataflow, no_colsweep, all_colsweep, no_chain, chain_wide
  * (rounds of at most this many blocks join the sweep chain, default 256), exact_dots, no_bcast_analysis
  * (every rank of a distributed preconditioner runs the global analysis instead of receiving rank 0's),
+ * apply_multi_panel (cpk_pc_apply_multi always on its panel kernels; set before building operators),
  * no_sched_resid, no_fused_resid, r0_xcd_chunk, tsolve_global, tsolve_sweep,
  * no_piggy, no_halo_merge, no_graph, no_fuse_last, no_tkr, no_minres_fuse, dist_graph, batch,
  * dist1 (a 1-rank communicator runs the distributed kernels; set before building operators),
@@ -223,6 +224,29 @@ int cpk_pc_apply_ldl_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_
  * panel solve runs it, info[4] = {columns per panel, kernel launches per panel solve, blocks
  * staged in LDS, blocks on the direct path through global memory} (multi-column sweep). */
 int cpk_pc_multi_info(cpk_pc M, int64_t *info);
+/* Y = M*X for a block of k right-hand sides, DEFINED column by column: column j of Y is what
+ * cpk_pc_apply returns for column j of X under the current nitref, itref_tol and force_itref, bit
+ * for bit -- the reference's double(op), one op*e per column (opLDL2.m:138-149).  (The reference's
+ * own matrix path, multiply on an N x k argument, takes norm(r) as a matrix 2-norm and x(1:n) as
+ * a linear index; it is not reproduced.)  Each column runs the loop of opLDL2.m:174-185 with its
+ * own predicate: columns of one panel stop refining at different steps, and a column that
+ * stopped is not touched again.  Layout and checks as cpk_pc_apply_ldl_multi: column-major,
+ * ldx, ldy >= N and k >= 0 (CPK_ERR_DIM otherwise; k == 0 does nothing); rows [N, ldy) of Y are
+ * not touched; X and Y may not overlap (CPK_ERR_ARGS).  nit (may be NULL) receives k counts, the
+ * refinement solves each column took, 0...nitref; in the device form d_nit is a device pointer.
+ * The columns go in panels of 8 through kernels that stream the factor twice per solve and Kp
+ * once per residual for the whole panel; a panel below the measured break-even (DESIGN.md
+ * section 5, the refined block apply) runs as a loop of single-column applies unless the engine
+ * option apply_multi_panel forces the panel kernels -- the bits are the same either way.  The
+ * predicate's norms are plain sums in a fixed order (also under exact_dots), so the block apply
+ * is deterministic from run to run; their last bits may differ from cpk_pc_apply's, which can
+ * matter only at an exact tie ||r|| == itref_tol*||x||.  Single GPU (CPK_ERR_UNSUPPORTED on a
+ * distributed preconditioner), and CPK_ERR_UNSUPPORTED, the state untouched, while the handle
+ * semantics of residual_update are in effect (cpk_pc_set_handle with residual_update set: one
+ * state vector). */
+int cpk_pc_apply_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit);
+int cpk_pc_apply_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
+                              int32_t *d_nit);
 /* x = Kp*b (opLDL2.divide, opLDL2.m:193-195). */
 int cpk_pc_divide(cpk_pc M, const double *b, double *x);
 int cpk_pc_get_info(cpk_pc M, cpk_pc_info *info);

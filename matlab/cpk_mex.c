@@ -10,7 +10,9 @@
  *   y = cpk_mex('pc_apply', h, x)               % y = M*x                  (opLDL2.m:161-188)
  *   Y = cpk_mex('pc_apply_ldl', h, X)           % Y = M'*X = conj(M)*X, X dense N x k: the bare
  *                                               % factor composite         (opLDL2.m:127-136)
- *   x = cpk_mex('pc_divide', h, b)              % x = Kp*b                 (opLDL2.m:193-195)
+ *   Y = cpk_mex('pc_apply_multi', h, X)         % Y(:,j) = M*X(:,j), X dense N x k: the refined
+ *                                               % apply column by column   (opLDL2.m:138-149, 161-188)
+ *   x = cpk_mex('pc_divide', h, b)             % x = Kp*b                 (opLDL2.m:193-195)
  *       cpk_mex('pc_destroy', h)
  *   [x, y, stats, flag] = cpk_mex('method', name, b, A, C, h, opts)
  *                                               % method(b, A, C, M, opts) (kernels/cp*.m)
@@ -180,7 +182,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     mxGetString(prhs[0], cmd, sizeof cmd);
     {   /* argument counts before anything is converted or a device is touched */
         static const struct { const char *cmd; int nrhs; } need[] = {
-            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
+            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_apply_multi", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
             {"method", 6}, {"reg_solve", 7}};
         int i;
         for (i = 0; i < (int)(sizeof need / sizeof need[0]); i++)
@@ -202,7 +204,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         cpk_pc M = to_pc(ARG(1));
         to_opts(ARG(2), &o);
         if ((st = cpk_pc_set(M, &o))) fail(st);
-    } else if (!strcmp(cmd, "pc_apply_ldl")) {
+    } else if (!strcmp(cmd, "pc_apply_ldl") || !strcmp(cmd, "pc_apply_multi")) {
+        const int ldl = cmd[9] == 'l';
         cpk_pc M = to_pc(ARG(1));
         cpk_pc_info info;
         int64_t k;
@@ -212,9 +215,11 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         k = (int64_t)mxGetN(ARG(2));
         plhs[0] = mxCreateDoubleMatrix((mwSize)info.N, (mwSize)k, mxREAL);
         if (k == 1)
-            st = cpk_pc_apply_ldl(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]));
+            st = ldl ? cpk_pc_apply_ldl(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]))
+                     : cpk_pc_apply(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]));
         else if (k > 0 && info.N > 0) /* MATLAB stores a dense matrix column-major, leading dimension N */
-            st = cpk_pc_apply_ldl_multi(M, k, mxGetPr(ARG(2)), info.N, mxGetPr(plhs[0]), info.N);
+            st = ldl ? cpk_pc_apply_ldl_multi(M, k, mxGetPr(ARG(2)), info.N, mxGetPr(plhs[0]), info.N)
+                     : cpk_pc_apply_multi(M, k, mxGetPr(ARG(2)), info.N, mxGetPr(plhs[0]), info.N, NULL);
         if (st) fail(st);
     } else if (!strcmp(cmd, "pc_apply") || !strcmp(cmd, "pc_divide")) {
         cpk_pc M = to_pc(ARG(1));

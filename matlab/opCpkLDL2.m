@@ -5,7 +5,9 @@ classdef opCpkLDL2 < opSpot
 %   M = opCpkLDL2(A, B, C) represents inv([A B'; B C]) exactly as opLDL2(A, B, C) does:
 %   same public properties (nitref, itref_tol, force_itref, residual_update), same setter
 %   semantics (opLDL2.m:97-115), same multiply (opLDL2.m:161-188) and divide (:193-195).
-%   The factor lives in HBM; M*z costs one PCIe round trip of z.
+%   The factor lives in HBM; M*z costs one PCIe round trip of z.  M*X with an n-by-k matrix
+%   is M on every column (cpk_mex 'pc_apply_multi'): y(:,j) = M*x(:,j) bit for bit, each column
+%   with its own refinement predicate -- what double(op) computes, not opLDL2's matrix path.
 %
 %   Spot operators are value objects.  The properties are therefore sent with every
 %   multiply, so copies keep independent settings as they do with opLDL2.
@@ -85,7 +87,15 @@ classdef opCpkLDL2 < opSpot
       function y = multiply(op, x, mode) %#ok<INUSD>
          cpk_mex('pc_set', op.h.id, struct('nitref', op.nitref, 'itref_tol', op.itref_tol, ...
                  'force_itref', double(op.force_itref), 'residual_update', double(op.residual_update)));
-         y = cpk_mex('pc_apply', op.h.id, full(x));
+         if size(x, 2) == 1
+            y = cpk_mex('pc_apply', op.h.id, full(x));
+         else
+            % a block M*X (sweepflag hands multiply the whole matrix): column by column on the
+            % device, y(:,j) = M*x(:,j) bit for bit, each column with its own refinement
+            % predicate.  opLDL2's own matrix path (norm(r) a matrix 2-norm, x(1:n) a linear
+            % index) is not reproduced.
+            y = cpk_mex('pc_apply_multi', op.h.id, full(x));
+         end
       end
       function x = divide(op, b, mode) %#ok<INUSD>
          x = cpk_mex('pc_divide', op.h.id, full(b));
