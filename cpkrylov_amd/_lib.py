@@ -102,6 +102,17 @@ _SIGS = {
     "cpk_reg_solve": ([vp, C.c_int, P(C.c_double), vp, vp, vp, vp, P(Opts), P(C.c_double), P(Stats), P(vp)],
                       C.c_int),
     "cpk_reg_solve_device": ([vp, C.c_int, vp, vp, vp, vp, vp, P(Opts), vp, P(Stats)], C.c_int),
+    "cpk_method_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, vp, vp, P(Opts), P(C.c_double),
+                                C.c_int64, P(C.c_double), C.c_int64, P(Stats), P(C.c_int)], C.c_int),
+    "cpk_method_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, P(Opts), vp, C.c_int64,
+                                       P(Stats), P(C.c_int)], C.c_int),
+    "cpk_reg_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, vp, vp, vp, P(Opts), P(C.c_double),
+                             C.c_int64, P(Stats), P(C.c_int)], C.c_int),
+    "cpk_reg_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, P(Opts), vp, C.c_int64,
+                                    P(Stats), P(C.c_int)], C.c_int),
+    "cpk_debug_spmm": ([vp, vp, vp, vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double)],
+                       C.c_int),
+    "cpk_debug_spmm_time": ([vp, vp, vp, vp, C.c_int, C.c_int, P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_reg_shift_device": ([vp, vp, vp, vp, vp, vp, vp, vp, P(C.c_int)], C.c_int),
     "cpk_profile_kernels": ([vp, vp, vp, vp, C.c_int, P(Profile)], C.c_int),
     "cpk_debug_pipe_stamps": ([P(C.c_uint64), C.c_int, P(C.c_int)], C.c_int),

@@ -567,14 +567,79 @@ def _new_stats(cap):
     return st, hist, lq, qr
 
 
+BLOCK_METHODS = ("cg", "minres")  # the methods with a lockstep block solve (cpk_method_solve_multi)
+
+
+def _is_block(b):
+    """An n x k array with k != 1 is a block of right-hand sides; a vector or an n x 1 array keeps
+    the single-column path and return shapes (the convention of opLDL2.__mul__ / apply_block)."""
+    return b.ndim == 2 and b.shape[1] != 1
+
+
+def _block_call(name, k, opts, n, m, call, raise_on_error):
+    """One block entry: per-column stats buffers and statuses around `call(stats_array, status_array)`;
+    returns (the C stats, stats list, flag list, the error to raise or None); a refusal or a failure
+    of the whole call raises at once, a failing column gives an error carrying `columns` (the
+    caller adds `partial`)."""
+    if name not in BLOCK_METHODS:
+        raise CpkError(_lib.CPK_ERR_UNSUPPORTED,
+                       f"cp{name} takes one right-hand side; the block solve covers cpcg and cpminres")
+    cap = _hist_cap(name, opts, n, m)
+    sts = (_lib.Stats * max(k, 1))()
+    hists = [np.zeros(cap) for _ in range(k)]
+    for j in range(k):
+        sts[j].hist, sts[j].hist_cap = _dptr(hists[j]), cap
+    status = (C.c_int * max(k, 1))()
+    rc = call(sts, status)
+    columns = [int(status[j]) for j in range(k)]
+    if rc != _lib.CPK_OK and not any(columns):
+        check(rc)  # refused, or failed as a whole: nothing was written
+    stats, flags = [], []
+    for j in range(k):
+        st, fl = _stats_from(name, sts[j], hists[j], None, None)
+        if columns[j]:
+            fl["error"] = columns[j]
+        stats.append(st)
+        flags.append(fl)
+    err = None
+    if rc != _lib.CPK_OK:
+        msg = lib.cpk_last_error().decode()
+        err = (IndefiniteError if rc == _lib.CPK_ERR_INDEFINITE else CpkError)(rc, msg)
+        err.columns = columns
+        flags[columns.index(rc) if rc in columns else 0].setdefault("message", msg)
+    return sts, stats, flags, (err if raise_on_error else None)
+
+
+def _method_block(name, b, Am, Cmat, M, opts, raise_on_error):
+    n, m = Am.shape[0], Cmat.shape[0]
+    if b.shape[0] != n:
+        raise CpkError(_lib.CPK_ERR_DIM, "b must have n rows")
+    k = b.shape[1]
+    Bf = np.asfortranarray(b)
+    X, Y = np.zeros((n, k), order="F"), np.zeros((m, k), order="F")
+
+    def call(sts, status):
+        return lib.cpk_method_solve_multi(M.ctx.h, _lib.METHODS[name], k, _dptr(Bf), max(n, 1), Am.h, Cmat.h, M.h,
+                                          C.byref(make_opts(opts)), _dptr(X), max(n, 1), _dptr(Y), max(m, 1), sts, status)
+
+    _, stats, flags, err = _block_call(name, k, opts, n, m, call, raise_on_error)
+    if err is not None:
+        err.partial = (X, Y, stats, flags)
+        raise err
+    return X, Y, stats, flags
+
+
 def _method(name):
-    def run(b, A, Cm, M, opts=None):
+    def run(b, A, Cm, M, opts=None, raise_on_error=True):
         if not isinstance(M, opLDL2):
             raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
         ctx = M.ctx
         Am, Cmat = _as_matrix(A, ctx), _as_matrix(Cm, ctx)
         n, m = Am.shape[0], Cmat.shape[0]
-        b = np.ascontiguousarray(b, dtype=np.float64).ravel()
+        b = np.asarray(b, dtype=np.float64)
+        if _is_block(b):
+            return _method_block(name, b, Am, Cmat, M, opts, raise_on_error)
+        b = np.ascontiguousarray(b).ravel()
         if b.shape[0] != n:
             raise CpkError(_lib.CPK_ERR_DIM, "b must have n entries")
         x, y = np.zeros(n), np.zeros(m)
@@ -586,7 +651,14 @@ def _method(name):
 
     run.__name__ = "cp" + name
     run._cpk_method = name
-    run.__doc__ = f"[x, y, stats, flag] = cp{name}(b, A, C, M, opts)  (kernels/cp{name}.m)"
+    run.__doc__ = (f"[x, y, stats, flag] = cp{name}(b, A, C, M, opts)  (kernels/cp{name}.m).\n\n"
+                   "An n x k array b with k != 1 is a block of right-hand sides (cpcg and cpminres; the other "
+                   "methods raise CPK_ERR_UNSUPPORTED): the k columns are solved in lockstep on the GPU "
+                   "(cpk_method_solve_multi), each column exactly as if solved alone, and the call returns "
+                   "X (n x k), Y (m x k) and stats, flag as lists of k dicts.  opts['print'] is ignored for a "
+                   "block.  A column that hits the reference's indefinite stop raises CpkError carrying "
+                   "`columns` (the per-column status codes) and `partial` (X, Y, stats, flag); with "
+                   "raise_on_error=False the results are returned with flag[j]['error'] set instead.")
     return run
 
 
@@ -598,8 +670,50 @@ cpgmres = _method("gmres")
 cpdqgmres = _method("dqgmres")
 
 
-def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None):
-    """[x, stats, flag] = reg_cpkrylov(method, b, A, B, C, G, opts)   (reg_cpkrylov.m:1-180)."""
+_PC_PROPS = ("nitref", "itref_tol", "force_itref", "residual_update")
+
+
+def _reg_block(name, b, mats, opts, ctx, raise_on_error):
+    """reg_cpkrylov for an N x k block: M = opLDL2(G, B, -C) built once with the preconditioner
+    fields of opts (reg_cpkrylov.m:128-148), then the shift, the method and the recovery per
+    column (reg_cpkrylov.m:152-175, cpk_reg_solve_multi)."""
+    Am, Bm, Cmat, Gm = mats
+    n, m = Am.shape[0], Bm.shape[0]
+    if b.shape[0] != n + m:
+        raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m rows")
+    if name not in BLOCK_METHODS:
+        raise CpkError(_lib.CPK_ERR_UNSUPPORTED,
+                       f"cp{name} takes one right-hand side; the block solve covers cpcg and cpminres")
+    negC = sp.csr_matrix((-Cmat._val, Cmat._ind, Cmat._ptr.astype(np.int64)), shape=Cmat.shape)
+    M = opLDL2(Gm, Bm, negC, ctx=ctx)
+    props = {k: opts[k] for k in _PC_PROPS if opts and k in opts}
+    if props:
+        M._set(**props)
+    k, N = b.shape[1], n + m
+    Bf = np.asfortranarray(b)
+    X = np.zeros((N, k), order="F")
+
+    def call(sts, status):
+        return lib.cpk_reg_solve_multi(ctx.h, _lib.METHODS[name], k, _dptr(Bf), max(N, 1), Am.h, Bm.h, Cmat.h, M.h,
+                                       C.byref(make_opts(opts)), _dptr(X), max(N, 1), sts, status)
+
+    sts, stats, flags, err = _block_call(name, k, opts, n, m, call, raise_on_error)
+    for j in range(k):
+        stats[j]["ptime"], stats[j]["stime"] = M.ptime, sts[j].stime
+    if stats:
+        stats[0]["M"] = M
+    if err is not None:
+        err.partial = (X, stats, flags)
+        raise err
+    return X, stats, flags
+
+
+def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None, raise_on_error=True):
+    """[x, stats, flag] = reg_cpkrylov(method, b, A, B, C, G, opts)   (reg_cpkrylov.m:1-180).
+
+    An N x k array b with k != 1 is a block (cpcg and cpminres): M is built once and returned in
+    stats[0]["M"], every column is shifted, solved and recovered as if alone, and x is N x k with
+    stats, flag lists of k dicts (see cpminres for the error convention)."""
     if any(v is None for v in (method, b, A, B, Cm, G)):
         raise CpkError(_lib.CPK_ERR_ARGS, "reg_cpkrylov: not enough inputs")
     name = getattr(method, "_cpk_method", method)
@@ -608,7 +722,10 @@ def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None):
     ctx = ctx or default_context()
     mats = [_as_matrix(M, ctx) for M in (A, B, Cm, G)]
     n, m = mats[0].shape[0], mats[1].shape[0]
-    b = np.ascontiguousarray(b, dtype=np.float64).ravel()
+    b = np.asarray(b, dtype=np.float64)
+    if _is_block(b):
+        return _reg_block(name, b, mats, opts, ctx, raise_on_error)
+    b = np.ascontiguousarray(b).ravel()
     if b.shape[0] != n + m:
         raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
     x = np.zeros(n + m)

@@ -714,6 +714,146 @@ int cpk_reg_shift_device(cpk_ctx ctx, const double *d_b, cpk_mat A, cpk_mat B, c
     API_END
 }
 
+// ---- the lockstep block solve: column j is method(b(:, j), A, C, M, opts) -------------------------
+// (kernels/cpcg.m:1, kernels/cpminres.m:1 per column).  Checks in the order of the block applies:
+// NULL arguments, then k and the leading dimensions, then what the entry does not support.
+static void check_solve_multi(cpk_mat A, cpk_mat C, const cpk_pc_s *M, int method, int64_t k, int64_t ld_n[2],
+                              int64_t ld_m, int64_t ld_N[2]) {
+    const int64_t n = A->h.nrows, m = C->h.nrows;
+    if (k < 0 || ld_n[0] < n || ld_n[1] < n || ld_m < m || ld_N[0] < n + m || ld_N[1] < n + m)
+        throw Error(CPK_ERR_DIM, "solve_multi: k >= 0 and leading dimensions >= the column length required");
+    check_method_dims(A, C, M);
+    const Precond &p = *M->p;
+    if (p.dist || M->ctx->c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
+    if (p.residual_update != 0 && p.handle)
+        throw Error(CPK_ERR_UNSUPPORTED, "block solve: the handle semantics of residual_update keep one state vector");
+    if (method != CPK_CG && method != CPK_MINRES)
+        throw Error(CPK_ERR_UNSUPPORTED, "block solve: cpcg and cpminres only (the other methods take one right-hand side)");
+}
+// the first failing column's status and message, after every column's outputs were written
+static int solve_multi_result(int rc, const std::string &msg) {
+    if (rc != CPK_OK) g_err = msg;
+    return rc;
+}
+
+int cpk_method_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double *d_B, int64_t ldb, cpk_mat A, cpk_mat C,
+                                  cpk_pc M, const cpk_opts *opts, double *d_XY, int64_t ldxy, cpk_stats *stats,
+                                  int *col_status) {
+    API_BEGIN
+    need(ctx && A && C && M && d_B && d_XY, "NULL argument");
+    int64_t ln[2] = {ldb, ldb}, lN[2] = {ldxy, ldxy};
+    check_solve_multi(A, C, M, method, k, ln, C->h.nrows, lN);
+    if (k == 0) return CPK_OK;
+    std::string msg;
+    const int rc = method_solve_multi_device(ctx->c, method, k, d_B, ldb, A->krylov_op(C, *M->p), *M->p, opts, d_XY, ldxy,
+                                             stats, col_status, &msg);
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+int cpk_method_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *B, int64_t ldb, cpk_mat A, cpk_mat C, cpk_pc M,
+                           const cpk_opts *opts, double *X, int64_t ldx, double *Y, int64_t ldy, cpk_stats *stats,
+                           int *col_status) {
+    API_BEGIN
+    need(ctx && A && C && M && B && X && (Y || !C->h.nrows), "NULL argument");
+    int64_t ln[2] = {ldb, ldx}, lN[2] = {A->h.nrows + C->h.nrows, A->h.nrows + C->h.nrows};
+    check_solve_multi(A, C, M, method, k, ln, ldy, lN);
+    if (k == 0) return CPK_OK;
+    Ctx &c = ctx->c;
+    Precond &p = *M->p;
+    const int64_t n = p.n, m = p.m, N = p.N;
+    // packed on the device; the caller's padding rows are never touched
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1), N1 = (size_t)std::max<int64_t>(N, 1);
+    DBuf<double> dB, dXY;
+    dB.alloc(n1 * (size_t)k), dXY.alloc(N1 * (size_t)k);
+    if (n) CPK_HIP(hipMemcpy2D(dB.p, n1 * sizeof(double), B, (size_t)ldb * sizeof(double), n * sizeof(double), (size_t)k,
+                               hipMemcpyHostToDevice));
+    auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    const int rc = method_solve_multi_device(c, method, k, dB.p, (int64_t)n1, A->krylov_op(C, p), p, opts, dXY.p, (int64_t)N1,
+                                             stats, col_status, &msg);
+    if (n) CPK_HIP(hipMemcpy2D(X, (size_t)ldx * sizeof(double), dXY.p, N1 * sizeof(double), n * sizeof(double), (size_t)k,
+                               hipMemcpyDeviceToHost));
+    if (m) CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dXY.p + n, N1 * sizeof(double), m * sizeof(double), (size_t)k,
+                               hipMemcpyDeviceToHost));
+    const double st = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats)
+        for (int64_t j = 0; j < k; j++) stats[j].stime = st;
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+// reg_cpkrylov.m:152-175 per column with an existing M: shift, method, recovery
+int cpk_reg_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double *d_B, int64_t ldb, cpk_mat A, cpk_mat B,
+                               cpk_mat C, cpk_pc M, const cpk_opts *opts, double *d_X, int64_t ldx, cpk_stats *stats,
+                               int *col_status) {
+    API_BEGIN
+    need(ctx && A && B && C && M && d_B && d_X, "NULL argument");
+    int64_t ln[2] = {A->h.nrows, A->h.nrows}, lN[2] = {ldb, ldx};
+    check_solve_multi(A, C, M, method, k, ln, C->h.nrows, lN);
+    if (k == 0) return CPK_OK;
+    const ShiftOps so = shift_ops(A, C, *M->p);
+    std::string msg;
+    const int rc = reg_solve_multi_device(ctx->c, method, k, d_B, ldb, A->krylov_op(C, *M->p), *so.A, *so.Bt, so.bt_colmin,
+                                          *M->p, opts, d_X, ldx, stats, col_status, &msg);
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *Bh, int64_t ldb, cpk_mat A, cpk_mat B, cpk_mat C,
+                        cpk_pc M, const cpk_opts *opts, double *X, int64_t ldx, cpk_stats *stats, int *col_status) {
+    API_BEGIN
+    need(ctx && A && B && C && M && Bh && X, "NULL argument");
+    int64_t ln[2] = {A->h.nrows, A->h.nrows}, lN[2] = {ldb, ldx};
+    check_solve_multi(A, C, M, method, k, ln, C->h.nrows, lN);
+    if (k == 0) return CPK_OK;
+    Precond &p = *M->p;
+    const int64_t N = p.N;
+    const size_t N1 = (size_t)std::max<int64_t>(N, 1);
+    DBuf<double> dB, dX;
+    dB.alloc(N1 * (size_t)k), dX.alloc(N1 * (size_t)k);
+    if (N) CPK_HIP(hipMemcpy2D(dB.p, N1 * sizeof(double), Bh, (size_t)ldb * sizeof(double), N * sizeof(double), (size_t)k,
+                               hipMemcpyHostToDevice));
+    const ShiftOps so = shift_ops(A, C, p);
+    std::string msg;
+    const int rc = reg_solve_multi_device(ctx->c, method, k, dB.p, (int64_t)N1, A->krylov_op(C, p), *so.A, *so.Bt,
+                                          so.bt_colmin, p, opts, dX.p, (int64_t)N1, stats, col_status, &msg);
+    if (N) CPK_HIP(hipMemcpy2D(X, (size_t)ldx * sizeof(double), dX.p, N1 * sizeof(double), N * sizeof(double), (size_t)k,
+                               hipMemcpyDeviceToHost));
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+// diagnostic: the panel Krylov product alone, host arrays (X, Y: N x k; dots: 2 k)
+int cpk_debug_spmm(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y,
+                   int64_t ldy, double *dots) {
+    API_BEGIN
+    need(ctx && A && C && M && X && Y && dots, "NULL argument");
+    check_method_dims(A, C, M);
+    Precond &p = *M->p;
+    const int64_t N = p.N;
+    if (k < 0 || ldx < N || ldy < N) throw Error(CPK_ERR_DIM, "debug_spmm: k >= 0 and leading dimensions >= N required");
+    if (k == 0) return CPK_OK;
+    const size_t N1 = (size_t)std::max<int64_t>(N, 1);
+    DBuf<double> dX, dY, dd;
+    dX.alloc(N1 * (size_t)k), dY.alloc(N1 * (size_t)k), dd.alloc(2 * (size_t)k);
+    if (N) CPK_HIP(hipMemcpy2D(dX.p, N1 * sizeof(double), X, (size_t)ldx * sizeof(double), N * sizeof(double), (size_t)k,
+                               hipMemcpyHostToDevice));
+    debug_spmm(ctx->c, A->krylov_op(C, p), p, k, dX.p, (int64_t)N1, dY.p, (int64_t)N1, dd.p);
+    if (N) CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, N1 * sizeof(double), N * sizeof(double), (size_t)k,
+                               hipMemcpyDeviceToHost));
+    CPK_HIP(hipMemcpy(dots, dd.p, 2 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
+int cpk_debug_spmm_time(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int kc, int reps, double *ms_panel, double *ms_single) {
+    API_BEGIN
+    need(ctx && A && C && M && ms_panel && ms_single, "NULL argument");
+    check_method_dims(A, C, M);
+    debug_spmm_time(ctx->c, A->krylov_op(C, *M->p), *M->p, kc, reps, ms_panel, ms_single);
+    API_END
+}
+
 int cpk_profile_kernels(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int reps, cpk_profile *out) {
     API_BEGIN
     need(ctx && out, "NULL argument");

@@ -424,11 +424,13 @@ struct MultiState {
     int32_t nit[kMultiKP];  // refinement solves column j took
 };
 // Yp = LDL * X (every column of the panel; the padding columns are zeros)
-void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel);
+void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel,
+                             const int *gate = nullptr);
 // Yp(:, j) += LDL * Rp(:, j) for the columns with act[j] != 0 (the others are not touched); a
 // panel with any == 0 leaves at once
 void launch_multisweep_refine(Ctx &c, const DFactor &F, const double *Rp, double *Yp, const int32_t *act, double *panel);
-void launch_multi_state(Ctx &c, int32_t *state, int kc, int steps);
+// gate (optional, device): a zero word leaves the panel with no active column (any = 0)
+void launch_multi_state(Ctx &c, int32_t *state, int kc, int steps, const int *gate = nullptr);
 // Rp = X - A*Yp, each row summed in spmv_stream's order; norms: part[b][2 * kMultiKP] = row block
 // b's sums of r^2 per column and, with first, of x^2 per column
 void launch_multi_resid(Ctx &c, const DMat &A, int kc, const double *X, int64_t ldx, const double *Yp, double *Rp,
@@ -439,7 +441,7 @@ void launch_multi_pred(Ctx &c, const double *part, int64_t nblk, double tol, int
                        double *xn2);
 // Y(0:N, j) = Yp(:, j) for j < kc, nit[j] = the state's count (nit may be null)
 void launch_multi_store(Ctx &c, int64_t N, int kc, const double *Yp, double *Y, int64_t ldy, const int32_t *state,
-                        int32_t *nit);
+                        int32_t *nit, const int *gate = nullptr);
 // the single-column apply's step count: *nit = v; *nit += (*active != 0)
 void launch_nit_set(Ctx &c, int32_t *nit, int v);
 void launch_nit_count(Ctx &c, int32_t *nit, const int *active);
@@ -646,6 +648,9 @@ struct Precond {
     void fill_vmaps();  // every mapped array from dl.Lx, dl.D, kpg
     // cached solvers (workspace + captured iteration graphs), keyed; see solvers.hip
     std::vector<std::pair<std::string, std::shared_ptr<void>>> solvers;
+    // the lockstep block solver (cpk_method_solve_multi), kept beside them under its own key so a
+    // block solve never evicts a single-column solver's graphs
+    std::pair<std::string, std::shared_ptr<void>> block_solver;
     // distributed rows of the Krylov operator and the shift products, which follow this
     // preconditioner's dof map (capi.cpp): keyed by (kind, matrix generation(s)); they die with it
     std::map<std::tuple<char, uint64_t, uint64_t>, std::unique_ptr<DMat>> dist_ops;
@@ -677,7 +682,11 @@ struct Precond {
     // predicate per column on the device; a panel of fewer than kApplyMultiMinCols columns runs
     // as a loop of apply() unless multi_panel (engine option apply_multi_panel) forces the panel
     // kernels.  Single GPU; CPK_ERR_UNSUPPORTED with the handle semantics of residual_update.
-    void apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit);
+    // gate (optional, device): a panel whose word is 0 costs nothing and writes nothing (the lockstep
+    // block solve's "any column running", solvers.hip); col_run (optional, device): column j's own
+    // run flag at col_run[j * col_run_stride], for the columns that go through apply()
+    void apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit,
+                     const int *gate = nullptr, const int *col_run = nullptr, size_t col_run_stride = 0);
     bool multi_panel = false;
     // the block apply's work arrays, allocated on first use (not part of DFactor::bytes): the
     // natural-order solution and residual panels, the row blocks' norm partials, the columns'

@@ -149,16 +149,17 @@ __global__ __launch_bounds__(kPredThreads) void multi_pred_kernel(const double *
 }
 
 // the panel's initial state: its kc columns active, no step taken (forced: `steps` for each)
-__global__ void multi_state_kernel(int32_t *state, int kc, int steps) {
+__global__ void multi_state_kernel(int32_t *state, int kc, int steps, const int *gate) {
     const int t = threadIdx.x;
     if (t < KP) state[t] = t < kc, state[KP + 1 + t] = t < kc ? steps : 0;
-    if (t == 0) state[KP] = kc > 0;
+    if (t == 0) state[KP] = kc > 0 && (!gate || *gate != 0);
 }
 
 // Y(:, j) = Yp(:, j) for the panel's kc columns (the padding columns and rows are never stored)
 // and their step counts
 __global__ void multi_store_kernel(int64_t N, int kc, const double *__restrict__ Yp, double *__restrict__ Y, int64_t ldy,
-                                   const int32_t *__restrict__ state, int32_t *__restrict__ nit) {
+                                   const int32_t *__restrict__ state, int32_t *__restrict__ nit, const int *gate) {
+    if (gate && *gate == 0) return;
     if (nit && blockIdx.x == 0 && threadIdx.x < (unsigned)kc) nit[threadIdx.x] = state[KP + 1 + threadIdx.x];
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N * KP; i += (int64_t)gridDim.x * blockDim.x) {
         const int j = (int)(i % KP);
@@ -184,8 +185,8 @@ void launch_nit_count(Ctx &c, int32_t *nit, const int *active) {
     CPK_HIP(hipGetLastError());
 }
 
-void launch_multi_state(Ctx &c, int32_t *state, int kc, int steps) {
-    hipLaunchKernelGGL(multi_state_kernel, dim3(1), dim3(64), 0, c.stream, state, kc, steps);
+void launch_multi_state(Ctx &c, int32_t *state, int kc, int steps, const int *gate) {
+    hipLaunchKernelGGL(multi_state_kernel, dim3(1), dim3(64), 0, c.stream, state, kc, steps, gate);
     CPK_HIP(hipGetLastError());
 }
 
@@ -209,9 +210,9 @@ void launch_multi_pred(Ctx &c, const double *part, int64_t nblk, double tol, int
 }
 
 void launch_multi_store(Ctx &c, int64_t N, int kc, const double *Yp, double *Y, int64_t ldy, const int32_t *state,
-                        int32_t *nit) {
+                        int32_t *nit, const int *gate) {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((N * KP + 255) / 256, 2048));
-    hipLaunchKernelGGL(multi_store_kernel, dim3(grid), dim3(256), 0, c.stream, N, kc, Yp, Y, ldy, state, nit);
+    hipLaunchKernelGGL(multi_store_kernel, dim3(grid), dim3(256), 0, c.stream, N, kc, Yp, Y, ldy, state, nit, gate);
     CPK_HIP(hipGetLastError());
 }
 

@@ -57,6 +57,7 @@ struct MultiRef {
     double *Yp = nullptr;          // backward output, natural order
     const int32_t *act = nullptr;  // [KP + 1] on the device
     int acc = 0;                   // backward: Yp += w for the active columns (0: Yp = w, every column)
+    const int *gate = nullptr;     // a zero word: the launch does nothing (a block solve's frozen panel)
 };
 
 template <bool BWD, int MODE>
@@ -69,6 +70,7 @@ __global__ __launch_bounds__(kMultiThreads) void multisweep_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TPB = kMultiThreads;
     static_assert(TPB % KP == 0, "a thread keeps its column across strided passes");
+    if (ref.gate && *ref.gate == 0) return;
     bool on = true;  // MODE 1: this thread's column (threadIdx.x % KP) is active
     if (MODE == 1 && ref.act) {
         if (ref.act[KP] == 0) return;
@@ -303,10 +305,11 @@ void launch_multisweep(Ctx &c, const DFactor &F, int64_t k, const double *X, int
     CPK_HIP(hipGetLastError());
 }
 
-void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel) {
-    MultiRef ref;
-    ref.Yp = Yp;
-    multi_fwd_rounds<0>(c, F, X, ldx, kc, panel, MultiRef{});
+void launch_multisweep_first(Ctx &c, const DFactor &F, int kc, const double *X, int64_t ldx, double *Yp, double *panel,
+                             const int *gate) {
+    MultiRef ref, fwd;
+    ref.Yp = Yp, ref.gate = gate, fwd.gate = gate;
+    multi_fwd_rounds<0>(c, F, X, ldx, kc, panel, fwd);
     multi_bwd_rounds<1>(c, F, nullptr, 0, kc, panel, ref);
     CPK_HIP(hipGetLastError());
 }

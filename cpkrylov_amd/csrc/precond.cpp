@@ -808,7 +808,8 @@ void Precond::ldl_solve_multi(int64_t k, const double *X, int64_t ldx, double *Y
 // The factor is streamed twice per solve and Kp once per residual for the whole panel.  Nothing
 // here waits for the device: the predicate, the step counts and the panel's "any column active"
 // word live in `mstate`, and every kernel of a panel with no active column leaves at once.
-void Precond::apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit) {
+void Precond::apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, int32_t *nit, const int *gate,
+                          const int *col_run, size_t col_run_stride) {
     if (dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: single-GPU only");
     if (residual_update != 0 && handle)
         throw Error(CPK_ERR_UNSUPPORTED, "multi-column apply: the handle semantics of residual_update keep one state vector");
@@ -823,7 +824,9 @@ void Precond::apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, in
         double *Yj = Y + j0 * ldy;
         int32_t *nj = nit ? nit + j0 : nullptr;
         if (kc < kApplyMultiMinCols && !multi_panel) {
-            for (int j = 0; j < kc; j++) apply(Xp + j * ldx, N, Yj + j * ldy, nullptr, nullptr, nj ? nj + j : nullptr);
+            for (int j = 0; j < kc; j++)
+                apply(Xp + j * ldx, N, Yj + j * ldy, col_run ? col_run + (size_t)(j0 + j) * col_run_stride : gate, nullptr,
+                      nj ? nj + j : nullptr);
             continue;
         }
         if (!ready) {
@@ -834,15 +837,15 @@ void Precond::apply_multi(int64_t k, const double *X, int64_t ldx, double *Y, in
             if (!mstate.n) mstate.alloc(sizeof(MultiState) / sizeof(int32_t)), mxn2.alloc(kMultiKP);
             ready = true;
         }
-        launch_multi_state(c, mstate.p, kc, forced ? steps : 0);
-        launch_multisweep_first(c, dF, kc, Xp, ldx, ypanel.p, panel.p);
+        launch_multi_state(c, mstate.p, kc, forced ? steps : 0, gate);
+        launch_multisweep_first(c, dF, kc, Xp, ldx, ypanel.p, panel.p, gate);
         for (int s = 0; s < steps; s++) {
             // forced: the norms are dead; the residual after the last step is never formed
             launch_multi_resid(c, dKp, kc, Xp, ldx, ypanel.p, rpanel.p, mstate.p, mpart.p, !forced, s == 0);
             if (!forced) launch_multi_pred(c, mpart.p, dKp.nblk, itref_tol, s, s == 0, mstate.p, mxn2.p);
             launch_multisweep_refine(c, dF, rpanel.p, ypanel.p, mstate.p, panel.p);
         }
-        launch_multi_store(c, N, kc, ypanel.p, Yj, ldy, mstate.p, nj);
+        launch_multi_store(c, N, kc, ypanel.p, Yj, ldy, mstate.p, nj, gate);
     }
 }
 

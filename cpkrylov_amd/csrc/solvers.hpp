@@ -13,6 +13,21 @@ void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, con
                       int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
 int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
                      double *d_b1, double *d_xy0);
+// The lockstep block solve: column j of XY (N x k, [x; y]) is method(b(:, j), A, C, M, opts)
+// (kernels/cpcg.m, kernels/cpminres.m), panels of kMultiKP columns sharing one Krylov product and
+// one panel apply per iteration.  stats / col_status: k entries or null.  Returns CPK_OK or the
+// status of the first failing column (its message in *errmsg); every column's outputs are written.
+int method_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int64_t ldb, const DMat &AC, Precond &M,
+                              const cpk_opts *opts, double *d_XY, int64_t ldxy, cpk_stats *stats, int *col_status,
+                              std::string *errmsg);
+// reg_cpkrylov's shift + method + recovery per column (reg_cpkrylov.m:152-175) of an N x k block
+int reg_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int64_t ldb, const DMat &AC,
+                           const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M, const cpk_opts *opts,
+                           double *d_X, int64_t ldx, cpk_stats *stats, int *col_status, std::string *errmsg);
+// diagnostic: the panel Krylov product alone (Y = blkdiag(A, C) * X, dots: 2 k inner products)
+void debug_spmm(Ctx &c, const DMat &AC, Precond &M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
+                double *d_dots);
+void debug_spmm_time(Ctx &c, const DMat &AC, Precond &M, int kc, int reps, double *ms_panel, double *ms_single);
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out);
 double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts);
 }  // namespace cpk

@@ -322,6 +322,60 @@ int cpk_reg_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_mat B
 int cpk_reg_solve_device(cpk_ctx ctx, int method, const double *d_b, cpk_mat A, cpk_mat B, cpk_mat C,
                          cpk_pc M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
 
+/* ---- a block of right-hand sides in lockstep (cpcg and cpminres) ------------------------ */
+/* [X(:,j), Y(:,j), stats(j), flag(j)] = method(B(:,j), A, C, M, opts) for j < k
+ * (kernels/cpcg.m:1, kernels/cpminres.m:1, column by column; the reference has no block solve).
+ * The columns iterate together on one GPU in panels of 8, sharing one pass over blkdiag(A, C)
+ * and one panel apply of M per iteration; k > 8 runs its panels one after the other.  A column
+ * whose own stop test holds freezes while the others run on, so its niters, history, solved, x
+ * and y are those of the column solved alone with the same opts (itmax = n by default, stopTol
+ * from its own initial residual); a column's result does not depend on k, on its position or on
+ * the other columns (a NaN stays in its column).  cpminres runs the unfused update (engine
+ * option no_minres_fuse), which the single-column solve equals bit for bit.
+ * B: n x k, X: n x k, Y: m x k, column-major with ldb, ldx >= n and ldy >= m; rows beyond the
+ * column length are not touched.  stats: k entries (each with its own hist / hist_cap; loop_ms is
+ * its panel's device time, bytes_moved the panel's model bytes / its columns) or NULL;
+ * col_status: k cpk_status values or NULL.  cpk_stats.status keeps its meaning (cpcglanczos only)
+ * and is always 0 here: which columns failed is reported in col_status alone, so pass it to tell
+ * them apart (a failed column also has solved = 0).  opts.print is ignored: nothing is printed.
+ * Returns CPK_OK when no column failed, else the status of the first failing column (the
+ * reference's indefinite / complex-norm stop, CPK_ERR_INDEFINITE: that column stops alone) with
+ * its index and message in cpk_last_error; every column's outputs are written either way.
+ * Refused before anything is written: NULL arguments (CPK_ERR_ARGS), k < 0 or a leading
+ * dimension below the column length (CPK_ERR_DIM), and with CPK_ERR_UNSUPPORTED a distributed
+ * preconditioner, the handle semantics of residual_update in effect (as cpk_pc_apply_multi), and
+ * methods other than CPK_CG and CPK_MINRES.  k == 0 does nothing.  Small blocks are not routed to
+ * single solves (DESIGN.md "Lockstep block solve" has the measured crossover). */
+int cpk_method_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *B, int64_t ldb, cpk_mat A, cpk_mat C,
+                           cpk_pc M, const cpk_opts *opts, double *X, int64_t ldx, double *Y, int64_t ldy,
+                           cpk_stats *stats, int *col_status);
+/* Same with device-resident d_B (n x k) and d_XY (N x k, [x; y] per column, ldxy >= N). */
+int cpk_method_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double *d_B, int64_t ldb, cpk_mat A,
+                                  cpk_mat C, cpk_pc M, const cpk_opts *opts, double *d_XY, int64_t ldxy,
+                                  cpk_stats *stats, int *col_status);
+/* reg_cpkrylov's shift + method + recovery (reg_cpkrylov.m:152-175) per column of an N x k block
+ * with an existing M: the shift is decided per column by any(b(n+1:N, j)), xy0 = M*[0; b2] of the
+ * shifted columns is one block apply, an unshifted column keeps xy0 = 0.  B, X: N x k, ldb, ldx
+ * >= N.  Statuses, refusals and stats as cpk_method_solve_multi (stime, ptime in every entry). */
+int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *B, int64_t ldb, cpk_mat A, cpk_mat Bm,
+                        cpk_mat C, cpk_pc M, const cpk_opts *opts, double *X, int64_t ldx, cpk_stats *stats,
+                        int *col_status);
+int cpk_reg_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double *d_B, int64_t ldb, cpk_mat A,
+                               cpk_mat Bm, cpk_mat C, cpk_pc M, const cpk_opts *opts, double *d_X, int64_t ldx,
+                               cpk_stats *stats, int *col_status);
+/* Diagnostic (not in the reference): the block solve's Krylov product alone.  Y(:, j) =
+ * blkdiag(A, C) * X(:, j), equal to cpk_mat_spmv on the column bit for bit, and dots[2 j],
+ * dots[2 j + 1] = <y_j(1:n), x_j(1:n)>, <y_j(n+1:N), x_j(n+1:N)> as the solvers take them (the
+ * exact sums under engine option exact_dots).  Host arrays, X, Y: N x k, ldx, ldy >= N. */
+int cpk_debug_spmm(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y,
+                   int64_t ldy, double *dots);
+
+/* Diagnostic: device time per launch (ms, HIP events, `reps` launches after a warm-up) of the
+ * panel product with kc <= 8 columns and, in the same run, of the single-column Krylov product
+ * on one column (tools/solve_multi_timing.py). */
+int cpk_debug_spmm_time(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int kc, int reps, double *ms_panel,
+                        double *ms_single);
+
 /* The driver's shift step alone (reg_cpkrylov.m:152-160): if any(b(n+1:N)), xy0 = M*[0; b2]
  * and b1 = b(1:n) - A*xy0(1:n) - B'*xy0(n+1:N); else b1 = b(1:n), xy0 = 0.  Device pointers:
  * d_b (N), d_b1 (n), d_xy0 (N).  *shifted reports whether the shift was taken. */

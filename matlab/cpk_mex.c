@@ -18,6 +18,15 @@
  *                                               % method(b, A, C, M, opts) (kernels/cp*.m)
  *   [x, stats, flag] = cpk_mex('reg_solve', name, b, A, B, C, G, opts)
  *                                               % reg_cpkrylov             (reg_cpkrylov.m:1-180)
+ *   [X, Y, stats, flag] = cpk_mex('method_solve_multi', name, B, A, C, h, opts)
+ *                                               % method(B(:,j), A, C, M, opts) for every column of
+ *                                               % the dense n x k B in lockstep (cpcg, cpminres;
+ *                                               % kernels/cpcg.m:1, kernels/cpminres.m:1); stats.niters,
+ *                                               % stats.histLen, stats.status and flag.solved are 1 x k,
+ *                                               % stats.residHistory is (itmax + 4) x k, column j valid
+ *                                               % up to histLen(j) and zero below.  A column on which the
+ *                                               % reference stops with its error does not raise: its
+ *                                               % stats.status is 1 (CPK_ERR_INDEFINITE), the others 0
  *
  * Errors: every failure becomes mexErrMsgIdAndTxt after the call's temporaries are freed
  * (mexErrMsgIdAndTxt does not return: it unwinds to MATLAB, so the device matrices this call
@@ -183,7 +192,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     {   /* argument counts before anything is converted or a device is touched */
         static const struct { const char *cmd; int nrhs; } need[] = {
             {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_apply_multi", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
-            {"method", 6}, {"reg_solve", 7}};
+            {"method", 6}, {"reg_solve", 7}, {"method_solve_multi", 6}};
         int i;
         for (i = 0; i < (int)(sizeof need / sizeof need[0]); i++)
             if (!strcmp(cmd, need[i].cmd) && nrhs < need[i].nrhs)
@@ -268,6 +277,50 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         release_tmp();
         put_stats(mid, &s, &plhs[1], &plhs[2]);
         free_hist(&s);
+    } else if (!strcmp(cmd, "method_solve_multi")) {
+        const int mid = method_id(ARG(1));
+        const char *sf[] = {"niters", "residHistory", "histLen", "status"};
+        const char *ff[] = {"solved"};
+        cpk_mat A, C;
+        cpk_pc M;
+        cpk_opts o;
+        cpk_stats *s;
+        int *status;
+        int64_t n, m, k, cap, j, i;
+        mxArray *X, *Y, *nit, *hist, *hlen, *stt, *solved;
+        if (!ARG(2) || mxIsSparse(ARG(2)) || mxIsComplex(ARG(2))) fail_msg("cpk:args", "B must be a dense real matrix");
+        A = to_mat(ARG(3)), C = to_mat(ARG(4));
+        M = to_pc(ARG(5));
+        n = (int64_t)mxGetM(ARG(3)), m = (int64_t)mxGetM(ARG(4));
+        if ((int64_t)mxGetM(ARG(2)) != n) fail_msg("cpk:dim", "B must have %lld rows", (long long)n);
+        k = (int64_t)mxGetN(ARG(2));
+        to_opts(ARG(6), &o);
+        cap = (int64_t)(o.has_itmax ? o.itmax : (double)n) + 4;
+        s = mxCalloc((size_t)(k > 0 ? k : 1), sizeof *s);
+        status = mxCalloc((size_t)(k > 0 ? k : 1), sizeof *status);
+        hist = mxCreateDoubleMatrix((mwSize)cap, (mwSize)k, mxREAL);
+        for (j = 0; j < k; j++) s[j].hist = mxGetPr(hist) + j * cap, s[j].hist_cap = cap;
+        X = mxCreateDoubleMatrix((mwSize)n, (mwSize)k, mxREAL);
+        Y = mxCreateDoubleMatrix((mwSize)m, (mwSize)k, mxREAL);
+        /* MATLAB stores a dense matrix column-major: the leading dimensions are the row counts */
+        st = cpk_method_solve_multi(ctx(), mid, k, mxGetPr(ARG(2)), n > 0 ? n : 1, A, C, M, &o, mxGetPr(X), n > 0 ? n : 1,
+                                    mxGetPr(Y), m > 0 ? m : 1, s, status);
+        for (j = 0, i = 0; j < k; j++) i |= status[j];
+        if (st && !i) fail(st); /* refused or failed as a whole; a failing column is reported in stats.status */
+        release_tmp();
+        nit = mxCreateDoubleMatrix(1, (mwSize)k, mxREAL), hlen = mxCreateDoubleMatrix(1, (mwSize)k, mxREAL);
+        stt = mxCreateDoubleMatrix(1, (mwSize)k, mxREAL), solved = mxCreateDoubleMatrix(1, (mwSize)k, mxREAL);
+        for (j = 0; j < k; j++) {
+            mxGetPr(nit)[j] = (double)s[j].niters, mxGetPr(hlen)[j] = (double)s[j].hist_len;
+            mxGetPr(stt)[j] = (double)status[j], mxGetPr(solved)[j] = s[j].solved ? 1.0 : 0.0;
+        }
+        plhs[0] = X, plhs[1] = Y;
+        plhs[2] = mxCreateStructMatrix(1, 1, 4, sf);
+        mxSetField(plhs[2], 0, "niters", nit), mxSetField(plhs[2], 0, "residHistory", hist);
+        mxSetField(plhs[2], 0, "histLen", hlen), mxSetField(plhs[2], 0, "status", stt);
+        plhs[3] = mxCreateStructMatrix(1, 1, 1, ff);
+        mxSetField(plhs[3], 0, "solved", solved);
+        mxFree(s), mxFree(status);
     } else {
         fail_msg("cpk:args", "cpk_mex: unknown command %s", cmd);
     }
