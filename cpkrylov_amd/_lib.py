@@ -112,6 +112,9 @@ _SIGS = {
                                     P(Stats), P(C.c_int)], C.c_int),
     "cpk_debug_spmm": ([vp, vp, vp, vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double)],
                        C.c_int),
+    "cpk_debug_dot": ([vp, C.c_int, C.c_int64, C.c_int, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, C.c_int,
+                       P(C.c_double)], C.c_int),
+    "cpk_debug_xnorm2": ([vp, C.c_int64, P(C.c_double), P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_debug_spmm_time": ([vp, vp, vp, vp, C.c_int, C.c_int, P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_reg_shift_device": ([vp, vp, vp, vp, vp, vp, vp, vp, P(C.c_int)], C.c_int),
     "cpk_profile_kernels": ([vp, vp, vp, vp, C.c_int, P(Profile)], C.c_int),

@@ -846,6 +846,42 @@ int cpk_debug_spmm(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int64_t k, const
     API_END
 }
 
+// diagnostic: nv inner products of host n-vectors through the solvers' reducing launches
+int cpk_debug_dot(cpk_ctx ctx, int kind, int64_t n, int nv, const double *A, int64_t lda, const double *B, int64_t ldb,
+                  int grid, double *out) {
+    API_BEGIN
+    need(ctx && A && B && out, "NULL argument");
+    need(kind == 0 || kind == 1, "debug_dot: kind is 0 (ewred) or 1 (ewtred)");
+    need(nv == 1 || nv == 2 || nv == 4, "debug_dot: nv is 1, 2 or 4");
+    need(n >= 0 && lda >= n && ldb >= n, "debug_dot: n >= 0 and leading dimensions >= n required");
+    need(grid >= 0, "debug_dot: grid >= 0 required");
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+    DBuf<double> dA, dB, dd;
+    dA.alloc(n1 * (size_t)nv), dB.alloc(n1 * (size_t)nv), dd.alloc((size_t)nv);
+    if (n) {
+        CPK_HIP(hipMemcpy2D(dA.p, n1 * sizeof(double), A, (size_t)lda * sizeof(double), n * sizeof(double), (size_t)nv,
+                            hipMemcpyHostToDevice));
+        CPK_HIP(hipMemcpy2D(dB.p, n1 * sizeof(double), B, (size_t)ldb * sizeof(double), n * sizeof(double), (size_t)nv,
+                            hipMemcpyHostToDevice));
+    }
+    debug_dot(ctx->c, kind, n, nv, dA.p, (int64_t)n1, dB.p, (int64_t)n1, grid, dd.p);
+    CPK_HIP(hipMemcpy(out, dd.p, (size_t)nv * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
+// diagnostic: out[i] = xnorm2(a[i], b[i]) (xacc.hpp) on the device, host arrays
+int cpk_debug_xnorm2(cpk_ctx ctx, int64_t n, const double *a, const double *b, double *out) {
+    API_BEGIN
+    need(ctx && a && b && out, "NULL argument");
+    need(n >= 0, "debug_xnorm2: n >= 0 required");
+    if (n == 0) return CPK_OK;
+    DBuf<double> da, db, dout;
+    h2d(da, a, (size_t)n), h2d(db, b, (size_t)n), dout.alloc((size_t)n);
+    debug_xnorm2(ctx->c, n, da.p, db.p, dout.p);
+    CPK_HIP(hipMemcpy(out, dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
 int cpk_debug_spmm_time(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int kc, int reps, double *ms_panel, double *ms_single) {
     API_BEGIN
     need(ctx && A && C && M && ms_panel && ms_single, "NULL argument");

@@ -152,14 +152,16 @@ __global__ void ewred_fin_kernel(F f, const double *tot) {
     if (threadIdx.x || blockIdx.x) return;
     if (f.setup()) f.fin(tot);
 }
+// grid: 0 for the solvers' own ew_grid(N); cpk_debug_dot passes another one (<= kEwGrid)
 template <int NV, class F>
-inline void launch_ewred(Ctx &c, int64_t N, const F &f) {
-    c.ensure_partials((size_t)ew_grid(N) * NV);
+inline void launch_ewred(Ctx &c, int64_t N, const F &f, int grid = 0) {
+    const int g = grid > 0 ? std::min(grid, kEwGrid) : ew_grid(N);
+    c.ensure_partials((size_t)g * NV);
     const bool dist = c.dist();
     if (c.exact())
-        hipLaunchKernelGGL((ewred_kernel<NV, F, XAcc>), dim3(ew_grid(N)), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
+        hipLaunchKernelGGL((ewred_kernel<NV, F, XAcc>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
     else
-        hipLaunchKernelGGL((ewred_kernel<NV, F>), dim3(ew_grid(N)), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
+        hipLaunchKernelGGL((ewred_kernel<NV, F>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
     if (dist) {
         allreduce_red(c, NV);
         hipLaunchKernelGGL(ewred_fin_kernel<F>, dim3(1), dim3(64), 0, c.stream, f, (const double *)c.red.p);
@@ -176,14 +178,14 @@ inline void launch_ewt(Ctx &c, int64_t N, const F &f) {
     hipLaunchKernelGGL(ewt_kernel<F>, dim3(ewt_grid(N)), dim3(kBlock), 0, c.stream, N, f);
 }
 template <int NV, class F>
-inline void launch_ewtred(Ctx &c, int64_t N, const F &f) {
-    c.ensure_partials((size_t)ewt_grid(N) * NV);
+inline void launch_ewtred(Ctx &c, int64_t N, const F &f, int grid = 0) {
+    const int g = grid > 0 ? std::min(grid, kEwGrid) : ewt_grid(N);
+    c.ensure_partials((size_t)g * NV);
     const bool dist = c.dist();
     if (c.exact())
-        hipLaunchKernelGGL((ewtred_kernel<NV, F, XAcc>), dim3(ewt_grid(N)), dim3(kBlock), 0, c.stream, N, f,
-                           red_buf(c));
+        hipLaunchKernelGGL((ewtred_kernel<NV, F, XAcc>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
     else
-        hipLaunchKernelGGL((ewtred_kernel<NV, F>), dim3(ewt_grid(N)), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
+        hipLaunchKernelGGL((ewtred_kernel<NV, F>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
     if (dist) {
         allreduce_red(c, NV);
         hipLaunchKernelGGL(ewred_fin_kernel<F>, dim3(1), dim3(64), 0, c.stream, f, (const double *)c.red.p);

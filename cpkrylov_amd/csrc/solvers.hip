@@ -2786,6 +2786,65 @@ void debug_spmm(Ctx &c, const DMat &AC, Precond &M, int64_t k, const double *d_X
     }
 }
 
+// Diagnostics (cpk_debug_dot, cpk_debug_xnorm2): the solvers' reductions and the exact mode's
+// norm([a b]) on the caller's values, so the accumulators can be tested at edge values that no
+// solve produces (tests/test_gpu_xacc.py)
+namespace {
+template <int NV>
+struct DebugDot {  // out[j] = <A(:, j), B(:, j)>
+    const double *A, *B;
+    int64_t lda, ldb;
+    double *out;
+    __device__ bool setup() { return true; }
+    template <class Acc>
+    __device__ void operator()(int64_t i, Acc *acc) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) dadd(acc[j], A[i + j * lda], B[i + j * ldb]);
+    }
+    template <class Acc>
+    __device__ void tile(int64_t i0, int64_t N, Acc *acc) {
+#pragma unroll
+        for (int e = 0; e < kTile; e++)
+            if (i0 + e * kBlock < N) (*this)(i0 + e * kBlock, acc);
+    }
+    __device__ void fin(const double *tot) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) out[j] = tot[j];
+    }
+};
+struct DebugXnorm2 {
+    const double *a, *b;
+    double *out;
+    __device__ bool setup() { return true; }
+    __device__ void operator()(int64_t i) { out[i] = xnorm2(a[i], b[i]); }
+};
+template <int NV>
+void debug_dot_nv(Ctx &c, int kind, int64_t n, const double *d_A, int64_t lda, const double *d_B, int64_t ldb, int grid,
+                  double *d_out) {
+    const DebugDot<NV> f{d_A, d_B, lda, ldb, d_out};
+    if (kind == 0) launch_ewred<NV>(c, n, f, grid);
+    else launch_ewtred<NV>(c, n, f, grid);
+}
+}  // namespace
+
+// kind 0: launch_ewred, kind 1: launch_ewtred (the kTile form); nv in {1, 2, 4}; grid 0: the
+// solvers' own.  Collective on a distributed context: every rank's d_out receives the global sums
+void debug_dot(Ctx &c, int kind, int64_t n, int nv, const double *d_A, int64_t lda, const double *d_B, int64_t ldb,
+               int grid, double *d_out) {
+    if (c.exact()) c.ensure_xacc((size_t)nv);
+    if (nv == 1) debug_dot_nv<1>(c, kind, n, d_A, lda, d_B, ldb, grid, d_out);
+    else if (nv == 2) debug_dot_nv<2>(c, kind, n, d_A, lda, d_B, ldb, grid, d_out);
+    else debug_dot_nv<4>(c, kind, n, d_A, lda, d_B, ldb, grid, d_out);
+    CPK_HIP(hipGetLastError());
+    CPK_HIP(hipStreamSynchronize(c.stream));
+}
+
+void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, double *d_out) {
+    launch_ew(c, n, DebugXnorm2{d_a, d_b, d_out});
+    CPK_HIP(hipGetLastError());
+    CPK_HIP(hipStreamSynchronize(c.stream));
+}
+
 // Diagnostic (cpk_debug_spmm_time): device time per launch (HIP events, `reps` back-to-back
 // launches after a warm-up) of the panel product with kc <= kMultiKP columns and, in the same run,
 // of the single-column Krylov product spmv_stream<EpiKrylov<PolPlainSpmv>> on one column

@@ -28,6 +28,11 @@ int reg_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int
 void debug_spmm(Ctx &c, const DMat &AC, Precond &M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
                 double *d_dots);
 void debug_spmm_time(Ctx &c, const DMat &AC, Precond &M, int kc, int reps, double *ms_panel, double *ms_single);
+// diagnostics: nv inner products of n-vectors through the solvers' reducing launches (device
+// pointers; collective on a distributed context), and out[i] = xnorm2(a[i], b[i])
+void debug_dot(Ctx &c, int kind, int64_t n, int nv, const double *d_A, int64_t lda, const double *d_B, int64_t ldb,
+               int grid, double *d_out);
+void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, double *d_out);
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out);
 double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts);
 }  // namespace cpk

@@ -10,6 +10,11 @@
 // Representation.  A thread accumulates into a floating-point expansion of kXK doubles (a TwoSum
 // cascade: every step is error-free, so the expansion plus whatever it deposits holds the exact
 // sum); the rare error term that outlives the cascade is deposited into the workgroup's digits.
+// A TwoSum is error-free only while none of its operations overflows, so the expansion's leading
+// term is kept at or below 2^1023 (XAcc::add): a term that would take it higher never enters the
+// cascade but goes straight to the digits (which have room for any sum of finite doubles), and
+// the expansion stays as it is.  Finite terms then never produce a non-finite intermediate,
+// however they are grouped, and the result is +-inf only when the exact sum rounds there.
 // At the end of the kernel the 64 lanes of a wave merge their expansions by shuffles, the waves
 // of the workgroup through LDS, and one lane deposits the workgroup's kXK terms as fixed-point
 // digits: value = sum d[i] * 2^(32 i - 1074), one signed 32-bit chunk per int64 word (every
@@ -77,19 +82,42 @@ struct XAcc {
         for (int k = 0; k < kXK; k++) t[k] = 0.0;
         ovf = o;
     }
-    __device__ __forceinline__ void add(double x) {
+    // r through the TwoSum cascade (no FMA contraction: -ffp-contract=off); returns what is left
+    __device__ __forceinline__ double cascade(double r) {
 #pragma unroll
-        for (int k = 0; k < kXK; k++) {  // TwoSum cascade (no FMA contraction: -ffp-contract=off)
-            const double s = t[k] + x, bb = s - t[k];
-            x = (t[k] - (s - bb)) + (x - bb);
+        for (int k = 0; k < kXK; k++) {
+            const double s = t[k] + r, bb = s - t[k];
+            r = (t[k] - (s - bb)) + (r - bb);
             t[k] = s;
         }
-        if (x != 0) xdeposit(ovf, x);  // beyond the expansion's reach (and every non-finite term)
+        return r;
     }
+    // TwoSum is error-free only while none of its operations overflows, and a finite sum
+    // s = t[0] + x is not enough for that: with |x| near DBL_MAX the recovered operand s - t[0]
+    // = x + (the rounding error of s) can round to inf.  So level 0 never holds more than 2^1023:
+    // when |t[0] + x| would exceed it (or x is not finite), x skips the cascade -- which then adds
+    // zero and changes nothing -- and goes to the digits, which hold any finite double and count
+    // a non-finite one.  With |s| <= 2^1023 its rounding error is at most 2^969, so
+    // |s - t[0]| <= |x| + 2^969 < DBL_MAX + 2^970, below the tie that rounds to inf; the other
+    // steps recover t[0] (at most 2^1023) and differences of nearly equal values.  Levels 1 and 2
+    // hold error terms, at most 2^-53 of level 0, and an error term added to level 0 (the merges)
+    // moves it by at most 2^970, which rounds back to 2^1023 at the most.  Depositing early is
+    // exact, only slower.  A select and the one deposit site, no second branch.
+    static constexpr double kXTop = 0x1p+1023;
+    __device__ __forceinline__ void add(double x) {
+        const bool fin = fabs(t[0] + x) <= kXTop;
+        const double r = cascade(fin ? x : 0.0);
+        if (r != 0 || !fin) xdeposit(ovf, fin ? r : x);  // beyond the expansion's reach, or its range
+    }
+    // The TwoProd pair with one test for both: once level 0 has taken p it holds at most 2^1023,
+    // and |e| <= ulp(p) / 2 <= 2^970 keeps it there; above the bound, or with a non-finite p, both
+    // terms go to the digits.
     __device__ __forceinline__ void add_prod(double a, double b) {
-        const double p = a * b;
-        add(p);
-        add(fma(a, b, -p));
+        const double p = a * b, e = fma(a, b, -p);
+        const bool fin = fabs(t[0] + p) <= kXTop;
+        const double rp = cascade(fin ? p : 0.0), re = cascade(fin ? e : 0.0);
+        if (rp != 0 || !fin) xdeposit(ovf, fin ? rp : p);
+        if (re != 0 || !fin) xdeposit(ovf, fin ? re : e);
     }
 };
 

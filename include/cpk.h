@@ -369,6 +369,17 @@ int cpk_reg_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double 
  * exact sums under engine option exact_dots).  Host arrays, X, Y: N x k, ldx, ldy >= N. */
 int cpk_debug_spmm(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int64_t k, const double *X, int64_t ldx, double *Y,
                    int64_t ldy, double *dots);
+/* Diagnostic (not in the reference): out[j] = <A(:, j), B(:, j)>, j < nv, taken exactly as the
+ * solvers take their sums: a plain dot functor through the element-wise reducing launch (kind 0)
+ * or its tiled form (kind 1), nv in {1, 2, 4}; the exact accumulator under engine option
+ * exact_dots, the fixed-tree sums otherwise.  grid = 0: the solvers' own grid for n; grid > 0:
+ * that many workgroups (at most the streaming kernels' cap).  Host arrays, A, B: n x nv, lda,
+ * ldb >= n; n = 0 gives +0.0.  On a context of several ranks the call is collective: every rank
+ * passes its local rows and receives the global sums.  Bad arguments: CPK_ERR_ARGS. */
+int cpk_debug_dot(cpk_ctx ctx, int kind, int64_t n, int nv, const double *A, int64_t lda, const double *B,
+                  int64_t ldb, int grid, double *out);
+/* Diagnostic: out[i] = the exact mode's norm([a[i] b[i]]) evaluated on the device, i < n. */
+int cpk_debug_xnorm2(cpk_ctx ctx, int64_t n, const double *a, const double *b, double *out);
 
 /* Diagnostic: device time per launch (ms, HIP events, `reps` launches after a warm-up) of the
  * panel product with kc <= 8 columns and, in the same run, of the single-column Krylov product

@@ -19,7 +19,6 @@ panel.  The oracle's result of a base column is computed once and shared.
 """
 import ctypes as C
 import functools
-from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -28,6 +27,7 @@ import scipy.sparse as sp
 import fixtures as F
 import structures as ST
 from oracle import oracle as O
+from xacc_cases import ref_exact
 
 pytestmark = pytest.mark.gpu
 
@@ -353,19 +353,7 @@ def _spmm(name, X):
     return Y, dots.reshape(k, 2), A, Cm
 
 
-def _xround(a, b):
-    """the correctly rounded exact inner product: the products summed as integers over a common
-    power of two, then one Fraction to float conversion (Python rounds it to nearest even)"""
-    import math
-    terms = []
-    for p, q in zip(a, b):
-        (mp, ep), (mq, eq) = math.frexp(float(p)), math.frexp(float(q))
-        terms.append((int(mp * 2 ** 53) * int(mq * 2 ** 53), ep + eq - 106))
-    if not terms:
-        return 0.0
-    e0 = min(e for _, e in terms)
-    total = sum(t << (e - e0) for t, e in terms)
-    return float(Fraction(total) * Fraction(2) ** e0)
+_xround = ref_exact  # the correctly rounded exact inner product (xacc_cases.py, reference A)
 
 
 @pytest.mark.parametrize("k", (1, 7, 8))
