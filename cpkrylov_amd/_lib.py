@@ -63,6 +63,9 @@ _SIGS = {
     "cpk_mat_create_csr": ([vp, C.c_int64, C.c_int64, P(C.c_int64), P(C.c_int32), P(C.c_double), P(vp)], C.c_int),
     "cpk_mat_destroy": ([vp], C.c_int),
     "cpk_mat_spmv": ([vp, P(C.c_double), P(C.c_double)], C.c_int),
+    "cpk_mat_set_values": ([vp, P(C.c_double), C.c_int64], C.c_int),
+    "cpk_mat_set_values_device": ([vp, vp, C.c_int64], C.c_int),
+    "cpk_mat_get_info": ([vp, P(C.c_int64)], C.c_int),
     "cpk_pc_create": ([vp, vp, vp, vp, P(C.c_double), P(vp)], C.c_int),
     "cpk_pc_create_hint": ([vp, vp, vp, vp, vp, P(C.c_double), P(vp)], C.c_int),
     "cpk_pc_destroy": ([vp], C.c_int),
@@ -77,6 +80,7 @@ _SIGS = {
     "cpk_pc_apply_ldl_multi": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64], C.c_int),
     "cpk_pc_apply_ldl_multi_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64], C.c_int),
     "cpk_pc_multi_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_pc_solver_info": ([vp, P(C.c_int64)], C.c_int),
     "cpk_pc_apply_multi": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_int32)], C.c_int),
     "cpk_pc_apply_multi_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp], C.c_int),
     "cpk_pc_divide": ([vp, P(C.c_double), P(C.c_double)], C.c_int),

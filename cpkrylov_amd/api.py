@@ -17,6 +17,7 @@ supported on the device path).  Errors raise CpkError / IndefiniteError.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import scipy.sparse as sp
@@ -188,6 +189,55 @@ class Matrix:
             check(lib.cpk_mat_create_csr(cx, M.shape[0], M.shape[1], self._ptr.ctypes.data_as(_P(C.c_int64)),
                                          self._ind.ctypes.data_as(_P(C.c_int32)), _dptr(self._val), C.byref(h)))
         self.h = h
+        self._csc = bool(csc)
+
+    def set_values(self, v):
+        """New values with the same sparsity, written into this handle (cpk_mat_set_values /
+        cpk_mat_set_values_device): the device copy, the Krylov operators cached on the handle and
+        the solvers a preconditioner cached (with their captured graphs) all stay and see the new
+        values at their next use; a preconditioner changes at its next `refactor`.  v is one of
+          * a NumPy array in the order of the canonical (sorted, duplicate-free) CSR data the
+            constructor passed down -- CSC data for a matrix created with csc=True;
+          * a scipy.sparse matrix, canonicalised as the constructor does; CPK_ERR_ARGS unless its
+            indptr and indices equal this handle's;
+          * a device tensor (anything with is_cuda, data_ptr(), dtype and is_contiguous(), e.g. a
+            torch tensor on the GPU) in the same order: float64 and contiguous; its current stream
+            is synchronised, then the values are gathered on the device with no host round trip.
+        """
+        if all(hasattr(v, a) for a in ("is_cuda", "data_ptr", "dtype", "is_contiguous")):
+            if not v.is_cuda:
+                v = v.detach().cpu().numpy()  # a host tensor: the NumPy path below
+            else:
+                if "float64" not in str(v.dtype) or not v.is_contiguous():
+                    raise CpkError(_lib.CPK_ERR_ARGS, "set_values: a contiguous float64 device tensor expected")
+                mod = sys.modules[type(v).__module__.split(".")[0]]  # the tensor's own library, already loaded
+                mod.cuda.current_stream(v.device).synchronize()
+                return self.set_values_device(v.data_ptr(), v.numel())
+        if sp.issparse(v):
+            M = (sp.csc_matrix if self._csc else sp.csr_matrix)(v, dtype=np.float64)
+            M.sum_duplicates()
+            M.sort_indices()
+            if M.shape != tuple(self.shape) or not (np.array_equal(M.indptr, self._ptr) and np.array_equal(M.indices, self._ind)):
+                raise CpkError(_lib.CPK_ERR_ARGS, "set_values: the sparsity differs from this matrix's")
+            v = M.data
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        check(lib.cpk_mat_set_values(self.h, _dptr(v) if v.size else None, v.size))
+        self._val = v.copy()
+
+    def set_values_device(self, ptr, count):
+        """The same from `count` float64 values at device address `ptr`, complete when the call is
+        made; blocks until they are consumed (cpk_mat_set_values_device)."""
+        check(lib.cpk_mat_set_values_device(self.h, C.c_void_p(int(ptr) if ptr else None), int(count)))
+        self._val = None  # this object's host values are no longer the matrix's
+
+    def info(self):
+        """Diagnostic (cpk_mat_get_info): sizes, the values generation (0 at creation, +1 per
+        successful set_values), whether a device copy exists, and the Krylov operators
+        blkdiag(self, C) cached on this handle."""
+        v = (C.c_int64 * 8)()
+        check(lib.cpk_mat_get_info(self.h, v))
+        return {"nrows": v[0], "ncols": v[1], "nnz": v[2], "entries": v[3], "values_generation": v[4],
+                "device_copy": bool(v[5]), "krylov_operators": v[6]}
 
     def __matmul__(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -250,7 +300,10 @@ class opLDL2:
     def refactor(self, A, B, Cm):
         """New values of (A, B, C) with the sparsity this operator was built with: the factors
         of opLDL2(A, B, C) recomputed on the device, symbolic analysis reused (cpk_pc_refactor;
-        an IPM outer iteration's rebuild of opLDL2, opLDL2.m:60-92).  Returns the seconds taken."""
+        an IPM outer iteration's rebuild of opLDL2, opLDL2.m:60-92).  Returns the seconds taken.
+        A, B, Cm may be `Matrix` objects: the handles this operator was built from, updated in
+        place with `Matrix.set_values`, are refactored from their device copies with nothing
+        converted or uploaded again."""
         mats = [_as_matrix(M, self.ctx) for M in (A, B, Cm)]
         pt = C.c_double()
         check(lib.cpk_pc_refactor(self.h, mats[0].h, mats[1].h, mats[2].h, C.byref(pt)))
@@ -331,6 +384,13 @@ class opLDL2:
 
     H = property(ctranspose)
     conj = ctranspose  # opLDL2.m:127-129: the same composite
+
+    def solver_info(self):
+        """Diagnostic (cpk_pc_solver_info): the solvers this operator caches and the hipGraph
+        instantiations they made so far -- a solve that replays cached graphs adds none."""
+        v = (C.c_int64 * 4)()
+        check(lib.cpk_pc_solver_info(self.h, v))
+        return dict(zip(("solvers", "graph_instantiations", "block_solvers", "block_graph_instantiations"), list(v)))
 
     def multi_info(self):
         """Diagnostic: the multi-column sweep of M' as launched (cpk_pc_multi_info)."""
@@ -684,6 +744,10 @@ def _reg_block(name, b, mats, opts, ctx, raise_on_error):
     if name not in BLOCK_METHODS:
         raise CpkError(_lib.CPK_ERR_UNSUPPORTED,
                        f"cp{name} takes one right-hand side; the block solve covers cpcg and cpminres")
+    if Cmat._val is None:
+        raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "reg_cpkrylov on a block builds -C on the host: C was last "
+                       "updated from device memory; pass its values with set_values from the host, or build "
+                       "M = opLDL2(G, B, -C) and call the method")
     negC = sp.csr_matrix((-Cmat._val, Cmat._ind, Cmat._ptr.astype(np.int64)), shape=Cmat.shape)
     M = opLDL2(Gm, Bm, negC, ctx=ctx)
     props = {k: opts[k] for k in _PC_PROPS if opts and k in opts}

@@ -31,17 +31,43 @@ struct cpk_simgroup_s {
     }
 };
 
+// blkdiag(A, C) on the device with the values generations of A and C it holds
+struct KrylovOp {
+    std::unique_ptr<DMat> m;
+    uint64_t va = 0, vc = 0;
+};
+
 struct cpk_mat_s {
     cpk_ctx_s *ctx = nullptr;
-    uint64_t gen = 0;
-    HCsr h;
-    std::unique_ptr<DMat> d;                          // lazily uploaded
-    std::map<uint64_t, std::unique_ptr<DMat>> ac;     // blkdiag(this, C) keyed by C's generation
+    uint64_t gen = 0;   // names the handle and its sparsity: never changes
+    uint64_t vgen = 0;  // values generation: +1 per successful cpk_mat_set_values[_device]
+    HCsr h;             // h.val may lag the device copy (h_stale): read the values through host()
+    ValueMap vm;        // stored entry <- entries of the creating call's value array
+    DValueMap dvm;      // its device copy, uploaded by the first update from device memory
+    bool h_stale = false;
+    bool hashed = false;
+    uint64_t phash = 0;
+    std::unique_ptr<DMat> d;                // lazily uploaded
+    std::map<uint64_t, KrylovOp> ac;        // blkdiag(this, C) keyed by C's generation
+    // the host copy with current values: downloaded after an update from device memory
+    const HCsr &host() {
+        if (h_stale) {
+            Ctx &c = ctx->c;
+            if (d->nnz) CPK_HIP(hipMemcpyAsync(h.val.data(), d->val.p, (size_t)d->nnz * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+            CPK_HIP(hipStreamSynchronize(c.stream));
+            h_stale = false;
+        }
+        return h;
+    }
+    uint64_t pattern_hash() {
+        if (!hashed) phash = pattern_hash_one(h), hashed = true;
+        return phash;
+    }
     const DMat &dev() {
         if (!ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
         if (!d) {
             d = std::make_unique<DMat>();
-            make_dmat(h, *d);
+            make_dmat(h, *d);  // no device copy yet: h is current
         }
         return *d;
     }
@@ -55,7 +81,7 @@ struct cpk_mat_s {
         auto &slot = M.dist_ops[{'K', gen, C->gen}];
         if (!slot) {
             auto m = std::make_unique<DMat>();
-            make_dist_dmat(dist_csr(blkdiag(h, C->h), *M.dofmap, ctx->c.rank, false, kKrylovSpare), ctx->c.nranks,
+            make_dist_dmat(dist_csr(blkdiag(host(), C->host()), *M.dofmap, ctx->c.rank, false, kKrylovSpare), ctx->c.nranks,
                            *m);
             slot = std::move(m);
         }
@@ -67,7 +93,7 @@ struct cpk_mat_s {
         auto &sb = M.dist_ops[{'B', gen, 0}];
         if (!sa || !sb) {
             const int64_t n = M.gn, N = M.gN;
-            HCsr a = h, bt;
+            HCsr a = host(), bt;
             a.ncols = N;
             bt.nrows = n, bt.ncols = N;
             bt.ptr.assign(n + 1, 0);
@@ -83,15 +109,39 @@ struct cpk_mat_s {
         }
         return {sa.get(), sb.get()};
     }
+    // this handle's n rows come first in blkdiag (hostsparse.cpp), C's after them, so the
+    // operator's value array is [A's values; C's values]: a refresh is one copy per stale half
+    void refresh_half(Ctx &c, cpk_mat_s *src, double *dst) {
+        const size_t bytes = (size_t)src->h.nnz() * sizeof(double);
+        if (!bytes) return;
+        if (src->d) {
+            CPK_HIP(hipMemcpyAsync(dst, src->d->val.p, bytes, hipMemcpyDeviceToDevice, c.stream));
+        } else {  // never uploaded, so its host copy is current
+            CPK_HIP(hipMemcpyAsync(dst, src->h.val.data(), bytes, hipMemcpyHostToDevice, c.stream));
+            CPK_HIP(hipStreamSynchronize(c.stream));
+        }
+    }
     const DMat &blkdiag_with(cpk_mat_s *C) {
         if (!ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
         auto it = ac.find(C->gen);
         if (it == ac.end()) {
-            auto m = std::make_unique<DMat>();
-            make_dmat(blkdiag(h, C->h), *m);
-            it = ac.emplace(C->gen, std::move(m)).first;
+            KrylovOp op;
+            op.va = vgen, op.vc = C->vgen;
+            op.m = std::make_unique<DMat>();
+            make_dmat(blkdiag(host(), C->host()), *op.m);
+            it = ac.emplace(C->gen, std::move(op)).first;
         }
-        return *it->second;
+        KrylovOp &op = it->second;
+        if (op.va != vgen || op.vc != C->vgen) {
+            // lazily, at the next use after an update of either matrix; the value array keeps
+            // its address, so graphs captured on the operator replay on the new values
+            DMat &m = *op.m;
+            if (m.nnz != h.nnz() + C->h.nnz() || m.nrows != h.nrows + C->h.nrows || (int64_t)m.val.n != m.nnz)
+                throw Error(CPK_ERR_ARGS, "blkdiag(A, C): the cached operator is not [A's entries; C's entries]");
+            if (op.va != vgen) refresh_half(ctx->c, this, m.val.p), op.va = vgen;
+            if (op.vc != C->vgen) refresh_half(ctx->c, C, m.val.p + h.nnz()), op.vc = C->vgen;
+        }
+        return *op.m;
     }
 };
 
@@ -310,7 +360,7 @@ int cpk_mat_create_csc(cpk_ctx ctx, int64_t nrows, int64_t ncols, const size_t *
     auto m = std::make_unique<cpk_mat_s>();
     m->ctx = ctx;
     m->gen = g_gen++;
-    m->h = csr_from_csc(nrows, ncols, jc, ir, pr);
+    m->h = csr_from_csc(nrows, ncols, jc, ir, pr, &m->vm);
     *out = m.release();
     API_END
 }
@@ -322,7 +372,7 @@ int cpk_mat_create_csr(cpk_ctx ctx, int64_t nrows, int64_t ncols, const int64_t 
     auto m = std::make_unique<cpk_mat_s>();
     m->ctx = ctx;
     m->gen = g_gen++;
-    m->h = csr_from_csr(nrows, ncols, rowptr, colind, val);
+    m->h = csr_from_csr(nrows, ncols, rowptr, colind, val, &m->vm);
     *out = m.release();
     API_END
 }
@@ -330,6 +380,65 @@ int cpk_mat_create_csr(cpk_ctx ctx, int64_t nrows, int64_t ncols, const int64_t 
 int cpk_mat_destroy(cpk_mat A) {
     API_BEGIN
     delete A;
+    API_END
+}
+
+// the checks of both value updates; nothing is touched before they pass
+static void check_set_values(cpk_mat A, const double *val, int64_t count, bool device) {
+    need(A != nullptr, "NULL matrix handle");
+    need(val != nullptr || count <= 0, "NULL value array");
+    if (count != A->vm.count) throw Error(CPK_ERR_DIM, "set_values: count differs from the creating call's entry count");
+    if (device && !A->ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
+    if (A->ctx && A->ctx->c.dist())
+        throw Error(CPK_ERR_UNSUPPORTED, "set_values: single-GPU only (a distributed preconditioner caches row slices by generation)");
+}
+
+int cpk_mat_set_values(cpk_mat A, const double *val, int64_t count) {
+    API_BEGIN
+    check_set_values(A, val, count, false);
+    const int64_t nnz = A->h.nnz();
+    if (A->d && nnz) {
+        // the device copy follows on the context stream, behind whatever still reads it; staged,
+        // so that a failed copy leaves both copies as they were
+        Ctx &c = A->ctx->c;
+        std::vector<double> v;
+        const double *src = val;  // the identity map: the caller's array is the stored order
+        if (!A->vm.identity) {
+            v.resize((size_t)nnz);
+            apply_value_map(A->vm, nnz, val, v.data());
+            src = v.data();
+        }
+        CPK_HIP(hipMemcpyAsync(A->d->val.p, src, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+        if (A->vm.identity) std::memcpy(A->h.val.data(), val, (size_t)nnz * sizeof(double));
+        else A->h.val.swap(v);
+    } else {
+        apply_value_map(A->vm, nnz, val, A->h.val.data());
+    }
+    A->h_stale = false;
+    A->vgen++;
+    API_END
+}
+
+int cpk_mat_set_values_device(cpk_mat A, const double *d_val, int64_t count) {
+    API_BEGIN
+    check_set_values(A, d_val, count, true);
+    Ctx &c = A->ctx->c;
+    const DMat &d = A->dev();
+    upload_value_map(A->vm, A->dvm);
+    launch_set_values(c, A->vm, A->dvm, d.nnz, d_val, d.val.p);
+    CPK_HIP(hipStreamSynchronize(c.stream));  // d_val is the caller's again
+    A->h_stale = d.nnz > 0;
+    A->vgen++;
+    API_END
+}
+
+int cpk_mat_get_info(cpk_mat A, int64_t info[8]) {
+    API_BEGIN
+    need(A && info, "NULL argument");
+    const int64_t v[8] = {A->h.nrows, A->h.ncols, A->h.nnz(), A->vm.count, (int64_t)A->vgen, A->d ? 1 : 0,
+                          (int64_t)A->ac.size(), 0};
+    std::memcpy(info, v, sizeof v);
     API_END
 }
 
@@ -352,8 +461,8 @@ int cpk_pc_create(cpk_ctx ctx, cpk_mat A11, cpk_mat B, cpk_mat C22, double *ptim
     need(ctx && A11 && B && C22 && out, "opLDL2: Invalid number of arguments.");
     auto pc = std::make_unique<cpk_pc_s>();
     pc->ctx = ctx;
-    if (ctx->c.dist()) pc->p.reset(precond_create_dist(ctx->c, A11->h, B->h, C22->h, nullptr));
-    else pc->p.reset(precond_create(ctx->c, A11->h, B->h, C22->h));
+    if (ctx->c.dist()) pc->p.reset(precond_create_dist(ctx->c, A11->host(), B->host(), C22->host(), nullptr));
+    else pc->p.reset(precond_create(ctx->c, A11->host(), B->host(), C22->host()));
     if (ptime) *ptime = pc->p->ptime;
     *out = pc.release();
     API_END
@@ -366,8 +475,8 @@ int cpk_pc_create_hint(cpk_ctx ctx, cpk_mat A11, cpk_mat B, cpk_mat C22, cpk_mat
     auto pc = std::make_unique<cpk_pc_s>();
     pc->ctx = ctx;
     if (ctx->c.dist())
-        pc->p.reset(precond_create_dist(ctx->c, A11->h, B->h, C22->h, Akry ? &Akry->h : nullptr));
-    else pc->p.reset(precond_create(ctx->c, A11->h, B->h, C22->h));
+        pc->p.reset(precond_create_dist(ctx->c, A11->host(), B->host(), C22->host(), Akry ? &Akry->host() : nullptr));
+    else pc->p.reset(precond_create(ctx->c, A11->host(), B->host(), C22->host()));
     if (ptime) *ptime = pc->p->ptime;
     *out = pc.release();
     API_END
@@ -381,7 +490,7 @@ int cpk_pc_refactor(cpk_pc M, cpk_mat A11, cpk_mat B, cpk_mat C22, double *ptime
         throw Error(CPK_ERR_DIM, "Incompatible dimensions.");
     if (!p.dl.ready)
         throw Error(CPK_ERR_UNSUPPORTED, "refactorization needs the device factorization (engine option host_factor off)");
-    if (pattern_hash(A11->h, B->h, C22->h) != p.pattern_hash)
+    if (pattern_hash_combine(A11->pattern_hash(), B->pattern_hash(), C22->pattern_hash()) != p.pattern_hash)
         throw Error(CPK_ERR_ARGS, "refactor: the sparsity of A11, B or C22 differs from the factored one");
     const double s = precond_refactor(p, A11->dev(), B->dev(), C22->dev());
     if (ptime) *ptime = s;
@@ -572,6 +681,15 @@ int cpk_pc_multi_info(cpk_pc M, int64_t *info) {
     if (M->p->dist) throw Error(CPK_ERR_UNSUPPORTED, "multi-column factor apply: single-GPU only");
     const MultiPlan &mp = multisweep_plan(M->p->dF);
     const int64_t v[4] = {kMultiKP, mp.launches, mp.staged, mp.direct};
+    std::memcpy(info, v, sizeof v);
+    API_END
+}
+
+int cpk_pc_solver_info(cpk_pc M, int64_t info[4]) {
+    API_BEGIN
+    need(M && info, "NULL argument");
+    const Precond &p = *M->p;
+    const int64_t v[4] = {(int64_t)p.solvers.size(), p.graph_inst, (int64_t)p.block_solvers.size(), p.block_graph_inst};
     std::memcpy(info, v, sizeof v);
     API_END
 }
@@ -979,13 +1097,13 @@ int cpk_reg_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_mat B
     if (!ctx || !b || !A || !B || !C || !G || !x) throw Error(CPK_ERR_ARGS, "reg_cpkrylov: not enough inputs");
     Ctx &c = ctx->c;
     // M = opLDL2(G, B, -C)   (reg_cpkrylov.m:128-132)
-    HCsr negC = C->h;
+    HCsr negC = C->host();
     for (auto &v : negC.val) v = -v;
     check_dist_method(c, method);
     auto pc = std::make_unique<cpk_pc_s>();
     pc->ctx = ctx;
-    if (c.dist()) pc->p.reset(precond_create_dist(c, G->h, B->h, negC, &A->h));
-    else pc->p.reset(precond_create(c, G->h, B->h, negC));
+    if (c.dist()) pc->p.reset(precond_create_dist(c, G->host(), B->host(), negC, &A->host()));
+    else pc->p.reset(precond_create(c, G->host(), B->host(), negC));
     Precond &p = *pc->p;
     apply_props(p, opts);  // reg_cpkrylov.m:135-148
     check_method_dims(A, C, pc.get());
@@ -1010,7 +1128,7 @@ int cpk_analyze(cpk_mat A11, cpk_mat B, cpk_mat C22, const char *options, cpk_an
     auto a = std::make_unique<cpk_analysis_s>();
     a->opts = engine_opts_from_env();
     if (options) apply_engine_options(a->opts, options);
-    a->an = analyze(A11->h, B->h, C22->h, a->opts);
+    a->an = analyze(A11->host(), B->host(), C22->host(), a->opts);
     *out = a.release();
     API_END
 }
@@ -1070,12 +1188,12 @@ int cpk_analysis_plan(cpk_analysis a, cpk_mat A, cpk_mat C, int nranks, int rank
          "A and C must match the analysis' n and m");
     auto p = std::make_unique<cpk_plan_s>();
     p->n = an.n, p->m = an.m;
-    p->ts = split_tree(an.F0, nranks, a->opts.split_tol, -1, &A->h);
+    p->ts = split_tree(an.F0, nranks, a->opts.split_tol, -1, &A->host());
     p->dm = make_dofmap(an.F0, p->ts, an.n);
     p->rp = make_rank_plan(an.F0, p->ts, p->dm, rank);
     p->kp = dist_csr(an.Kp, p->dm, rank, false);
-    p->ac = dist_csr(blkdiag(A->h, C->h), p->dm, rank, false);
-    p->ab = dist_csr(hstack_ab(A->h, an.Kp, an.n), p->dm, rank, true);
+    p->ac = dist_csr(blkdiag(A->host(), C->host()), p->dm, rank, false);
+    p->ab = dist_csr(hstack_ab(A->host(), an.Kp, an.n), p->dm, rank, true);
     *out = p.release();
     API_END
 }

@@ -218,6 +218,15 @@ struct DMat {
     size_t bytes() const { return ptr.bytes() + col.bytes() + val.bytes() + blk.bytes(); }
 };
 void make_dmat(const HCsr &a, DMat &d);
+// device copy of a matrix handle's value map, uploaded on the first update from device memory
+struct DValueMap {
+    bool ready = false;
+    DBuf<uint32_t> perm, sptr, src;
+};
+void upload_value_map(const ValueMap &vm, DValueMap &dm);
+// out (nnz stored entries) from the creating call's value order `in`, both on the device, on the
+// context stream (setvalues.hip); nothing is waited for
+void launch_set_values(Ctx &c, const ValueMap &vm, const DValueMap &dm, int64_t nnz, const double *in, double *out);
 struct DistCsr;
 void make_dist_dmat(const DistCsr &a, int nranks, DMat &d);
 // allgather the halo of x (local vector) into A.rbuf
@@ -648,9 +657,12 @@ struct Precond {
     void fill_vmaps();  // every mapped array from dl.Lx, dl.D, kpg
     // cached solvers (workspace + captured iteration graphs), keyed; see solvers.hip
     std::vector<std::pair<std::string, std::shared_ptr<void>>> solvers;
-    // the lockstep block solver (cpk_method_solve_multi), kept beside them under its own key so a
-    // block solve never evicts a single-column solver's graphs
-    std::pair<std::string, std::shared_ptr<void>> block_solver;
+    // the lockstep block solvers (cpk_method_solve_multi), kept beside them under their own keys so
+    // a block solve never evicts a single-column solver's graphs: at most two, one per block method
+    std::vector<std::pair<std::string, std::shared_ptr<void>>> block_solvers;
+    // hipGraphInstantiate calls made by the single-column solvers / the block solvers of this
+    // preconditioner so far, evicted ones included (cpk_pc_solver_info)
+    int64_t graph_inst = 0, block_graph_inst = 0;
     // distributed rows of the Krylov operator and the shift products, which follow this
     // preconditioner's dof map (capi.cpp): keyed by (kind, matrix generation(s)); they die with it
     std::map<std::tuple<char, uint64_t, uint64_t>, std::unique_ptr<DMat>> dist_ops;
@@ -723,7 +735,11 @@ Precond *precond_create(Ctx &c, const HCsr &A11, const HCsr &B, const HCsr &C22)
 // new values of A11, B, C22 (device CSR copies) with the sparsity the preconditioner was built
 // with: Kp and the numeric factorization on the device, symbolic analysis reused; returns seconds
 double precond_refactor(Precond &p, const DMat &A11, const DMat &B, const DMat &C22);
+// = pattern_hash_combine of the three matrices' pattern_hash_one: a handle's sparsity never
+// changes, so the C ABI hashes each matrix once per handle (capi.cpp)
 uint64_t pattern_hash(const HCsr &A11, const HCsr &B, const HCsr &C22);
+uint64_t pattern_hash_one(const HCsr &a);
+uint64_t pattern_hash_combine(uint64_t a11, uint64_t b, uint64_t c22);
 // device data uploaded ahead of precond_create (during the analysis, SymbolicHook)
 struct PrecondPre {
     DLdl dl;   // dldl_setup_sym done when dl.sym_ready

@@ -28,8 +28,24 @@ struct HCsr {
     int64_t nnz() const { return ptr.empty() ? 0 : ptr.back(); }
 };
 
-HCsr csr_from_csr(int64_t nr, int64_t nc, const int64_t *rp, const int32_t *ci, const double *v);
-HCsr csr_from_csc(int64_t nr, int64_t nc, const size_t *jc, const size_t *ir, const double *pr);
+// Value map of a converted matrix: where each stored entry's value comes from in the value array
+// of the call that created it (entry e of that array = the e-th entry the conversion read, so
+// e = 0 is v[rp[0]] / pr[jc[0]]).  New values with the same index arrays go through it instead of
+// through the conversion again (apply_value_map): the same stable column sort, the same
+// left-to-right sum of duplicates, so the same bits.
+//   identity: stored entry q <- entry q (rows sorted, no duplicates): no arrays
+//   perm:     stored entry q <- entry perm[q] (no duplicates)
+//   sptr/src: stored entry q <- entry src[sptr[q]] + entry src[sptr[q] + 1] + ... in that order
+struct ValueMap {
+    int64_t count = 0;  // entries of the creating call
+    bool identity = true;
+    std::vector<uint32_t> perm, sptr, src;
+};
+// vm (optional): receives the value map of the conversion
+HCsr csr_from_csr(int64_t nr, int64_t nc, const int64_t *rp, const int32_t *ci, const double *v, ValueMap *vm = nullptr);
+HCsr csr_from_csc(int64_t nr, int64_t nc, const size_t *jc, const size_t *ir, const double *pr, ValueMap *vm = nullptr);
+// out[q] (nnz stored entries) from the creating call's entries in[0 .. vm.count)
+void apply_value_map(const ValueMap &vm, int64_t nnz, const double *in, double *out);
 HCsr transpose(const HCsr &a);
 // Kp = [A B'; B C]  (opLDL2.m:81); throws CPK_ERR_DIM unless check_kp_dims passes
 void check_kp_dims(const HCsr &A, const HCsr &B, const HCsr &C);  // opLDL2.m:61-75

@@ -66,33 +66,89 @@ void transpose_pattern(int64_t N, const int64_t *Lp, const int32_t *Li, uint32_t
 }
 
 // Canonicalise: sort each row by column, sum duplicates (MATLAB sparse arrays never hold any).
-static void canonicalise(HCsr &a) {
+// from (optional): the creating call's entry of each entry of a (empty: its own index); vm
+// (optional): receives the value map, composed with from.
+static void canonicalise(HCsr &a, const std::vector<uint32_t> &from, ValueMap *vm) {
+    const int64_t nin = (int64_t)a.ind.size();
+    if (vm) {
+        if (nin > (int64_t)UINT32_MAX) throw Error(CPK_ERR_UNSUPPORTED, "more than 2^32 entries in one matrix");
+        *vm = ValueMap();
+        vm->count = nin;
+    }
+    // rows already strictly ascending: nothing moves and nothing is summed
+    bool clean = true;
+    for (int64_t i = 0; i < a.nrows && clean; i++)
+        for (int64_t p = a.ptr[i] + 1; p < a.ptr[i + 1]; p++)
+            if (a.ind[p - 1] >= a.ind[p]) {
+                clean = false;
+                break;
+            }
+    if (clean) {
+        bool same = true;  // a column-compressed input whose entries were already in row order
+        for (size_t q = 0; q < from.size() && same; q++) same = from[q] == q;
+        if (vm && !same) vm->identity = false, vm->perm = from;
+        return;
+    }
     std::vector<int64_t> ptr(a.nrows + 1, 0);
     std::vector<int32_t> ind;
     std::vector<double> val;
+    std::vector<uint32_t> sptr, src;  // sources of each stored entry, in the order they are summed
     ind.reserve(a.ind.size());
     val.reserve(a.val.size());
-    std::vector<std::pair<int32_t, double>> row;
+    if (vm) sptr.reserve(a.ind.size() + 1), src.reserve(a.ind.size());
+    struct Ent {
+        int32_t col;
+        uint32_t e;
+        double v;
+    };
+    std::vector<Ent> row;
+    bool dup = false;
     for (int64_t i = 0; i < a.nrows; i++) {
         row.clear();
-        for (int64_t p = a.ptr[i]; p < a.ptr[i + 1]; p++) row.emplace_back(a.ind[p], a.val[p]);
-        bool sorted = std::is_sorted(row.begin(), row.end(),
-                                     [](auto &x, auto &y) { return x.first < y.first; });
-        if (!sorted) std::stable_sort(row.begin(), row.end(), [](auto &x, auto &y) { return x.first < y.first; });
+        for (int64_t p = a.ptr[i]; p < a.ptr[i + 1]; p++) row.push_back({a.ind[p], from.empty() ? (uint32_t)p : from[p], a.val[p]});
+        bool sorted = std::is_sorted(row.begin(), row.end(), [](const Ent &x, const Ent &y) { return x.col < y.col; });
+        if (!sorted) std::stable_sort(row.begin(), row.end(), [](const Ent &x, const Ent &y) { return x.col < y.col; });
         for (size_t q = 0; q < row.size(); q++) {
-            if (!ind.empty() && (int64_t)ind.size() > ptr[i] && ind.back() == row[q].first)
-                val.back() += row[q].second;
-            else
-                ind.push_back(row[q].first), val.push_back(row[q].second);
+            if (!ind.empty() && (int64_t)ind.size() > ptr[i] && ind.back() == row[q].col) {
+                val.back() += row[q].v;
+                dup = true;
+            } else {
+                ind.push_back(row[q].col), val.push_back(row[q].v);
+                if (vm) sptr.push_back((uint32_t)src.size());
+            }
+            if (vm) src.push_back(row[q].e);
         }
         ptr[i + 1] = (int64_t)ind.size();
     }
     a.ptr.swap(ptr);
     a.ind.swap(ind);
     a.val.swap(val);
+    if (vm) {
+        vm->identity = false;
+        if (dup) {
+            sptr.push_back((uint32_t)src.size());
+            vm->sptr.swap(sptr), vm->src.swap(src);
+        } else {
+            vm->perm.swap(src);
+        }
+    }
 }
 
-HCsr csr_from_csr(int64_t nr, int64_t nc, const int64_t *rp, const int32_t *ci, const double *v) {
+void apply_value_map(const ValueMap &vm, int64_t nnz, const double *in, double *out) {
+    if (vm.identity) {
+        if (nnz) std::copy(in, in + nnz, out);
+    } else if (vm.sptr.empty()) {
+        for (int64_t q = 0; q < nnz; q++) out[q] = in[vm.perm[q]];
+    } else {
+        for (int64_t q = 0; q < nnz; q++) {
+            double s = in[vm.src[vm.sptr[q]]];
+            for (uint32_t t = vm.sptr[q] + 1; t < vm.sptr[q + 1]; t++) s += in[vm.src[t]];
+            out[q] = s;
+        }
+    }
+}
+
+HCsr csr_from_csr(int64_t nr, int64_t nc, const int64_t *rp, const int32_t *ci, const double *v, ValueMap *vm) {
     if (nr < 0 || nc < 0 || nr > INT32_MAX || nc > INT32_MAX) throw Error(CPK_ERR_DIM, "matrix dimensions out of range");
     if (nr > 0 && (!rp || (rp[nr] > 0 && (!ci || !v)))) throw Error(CPK_ERR_ARGS, "NULL CSR array");
     HCsr a;
@@ -107,15 +163,16 @@ HCsr csr_from_csr(int64_t nr, int64_t nc, const int64_t *rp, const int32_t *ci, 
         if (a.ptr[i + 1] < a.ptr[i]) throw Error(CPK_ERR_ARGS, "CSR row pointers not monotone");
     for (auto c : a.ind)
         if (c < 0 || c >= nc) throw Error(CPK_ERR_ARGS, "CSR column index out of range");
-    canonicalise(a);
+    canonicalise(a, {}, vm);
     return a;
 }
 
-HCsr csr_from_csc(int64_t nr, int64_t nc, const size_t *jc, const size_t *ir, const double *pr) {
+HCsr csr_from_csc(int64_t nr, int64_t nc, const size_t *jc, const size_t *ir, const double *pr, ValueMap *vm) {
     if (nr < 0 || nc < 0 || nr > INT32_MAX || nc > INT32_MAX) throw Error(CPK_ERR_DIM, "matrix dimensions out of range");
     if (nc > 0 && !jc) throw Error(CPK_ERR_ARGS, "NULL CSC array");
     size_t nnz = nc > 0 ? jc[nc] - jc[0] : 0;
     if (nnz && (!ir || !pr)) throw Error(CPK_ERR_ARGS, "NULL CSC array");
+    if (vm && nnz > (size_t)UINT32_MAX) throw Error(CPK_ERR_UNSUPPORTED, "more than 2^32 entries in one matrix");
     HCsr a;
     a.nrows = nr, a.ncols = nc;
     a.ptr.assign(nr + 1, 0);
@@ -127,14 +184,17 @@ HCsr csr_from_csc(int64_t nr, int64_t nc, const size_t *jc, const size_t *ir, co
     for (int64_t i = 0; i < nr; i++) a.ptr[i + 1] += a.ptr[i];
     a.ind.resize(nnz);
     a.val.resize(nnz);
+    std::vector<uint32_t> from(vm ? nnz : 0);
+    const size_t p0 = nc > 0 ? jc[0] : 0;
     std::vector<int64_t> next(a.ptr.begin(), a.ptr.end() - 1);
     for (int64_t j = 0; j < nc; j++)  // columns ascend, so every row comes out sorted
         for (size_t p = jc[j]; p < jc[j + 1]; p++) {
             int64_t q = next[ir[p]]++;
             a.ind[q] = (int32_t)j;
             a.val[q] = pr[p];
+            if (vm) from[q] = (uint32_t)(p - p0);
         }
-    canonicalise(a);
+    canonicalise(a, from, vm);
     return a;
 }
 

@@ -651,15 +651,23 @@ void Precond::fill_vmaps() {
         vmap_fill(*ctx, m.map.p, m.n, m.src == 0 ? dl.Lx.p : (m.src == 1 ? dl.D.p : kpg.p), m.dst);
 }
 
-uint64_t pattern_hash(const HCsr &A11, const HCsr &B, const HCsr &C22) {
+uint64_t pattern_hash_one(const HCsr &a) {
     uint64_t h = 1469598103934665603ull;  // FNV-1a over the dimensions, row pointers and columns
     auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
-    for (const HCsr *a : {&A11, &B, &C22}) {
-        mix((uint64_t)a->nrows), mix((uint64_t)a->ncols);
-        for (int64_t v : a->ptr) mix((uint64_t)v);
-        for (int32_t v : a->ind) mix((uint32_t)v);
-    }
+    mix((uint64_t)a.nrows), mix((uint64_t)a.ncols);
+    for (int64_t v : a.ptr) mix((uint64_t)v);
+    for (int32_t v : a.ind) mix((uint32_t)v);
     return h;
+}
+
+uint64_t pattern_hash_combine(uint64_t a11, uint64_t b, uint64_t c22) {
+    uint64_t h = 1469598103934665603ull;
+    for (uint64_t v : {a11, b, c22}) h = (h ^ v) * 1099511628211ull;
+    return h;
+}
+
+uint64_t pattern_hash(const HCsr &A11, const HCsr &B, const HCsr &C22) {
+    return pattern_hash_combine(pattern_hash_one(A11), pattern_hash_one(B), pattern_hash_one(C22));
 }
 
 // Single GPU: the host does the symbolic analysis, the device the numeric factorization

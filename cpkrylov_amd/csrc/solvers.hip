@@ -1682,6 +1682,7 @@ struct SolveCore {
                 CPK_HIP(hipStreamEndCapture(c.stream, &graph));
                 graphs[slot].first = graph;
                 CPK_HIP(hipGraphInstantiate(&graphs[slot].second, graph, nullptr, nullptr, 0));
+                M.graph_inst++;
             } catch (const Error &e) {
                 // a transport that cannot be captured (deterministic, so every rank lands here):
                 // end the capture, drop the graph and run this solver's batches eagerly
@@ -2472,6 +2473,7 @@ struct MultiCore {
                 CPK_HIP(hipStreamEndCapture(c.stream, &graph));
                 slot.first = graph;
                 CPK_HIP(hipGraphInstantiate(&slot.second, graph, nullptr, nullptr, 0));
+                M.block_graph_inst++;
             } catch (const Error &) {
                 hipGraph_t g2 = nullptr;
                 (void)hipStreamEndCapture(c.stream, &g2);
@@ -2629,11 +2631,16 @@ int method_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, 
     // any capture (it keys the captured graphs)
     c.ensure_partials(std::max<size_t>((size_t)std::max<int64_t>(AC.nblk, M.dKp.nblk) * 2, (size_t)kEwGrid * 2));
     const std::string key = block_key(c, M, AC, method);
-    if (M.block_solver.first != key || !M.block_solver.second) {
-        M.block_solver.second.reset();
-        M.block_solver = {key, std::shared_ptr<void>(new MultiCore(c, M, AC, method))};
+    // one per block method (cpcg, cpminres), so an outer loop that runs both on new values keeps
+    // replaying both sets of graphs; a third key (other properties or options) drops the oldest
+    auto slot = M.block_solvers.begin();
+    while (slot != M.block_solvers.end() && slot->first != key) ++slot;
+    if (slot == M.block_solvers.end()) {
+        if (M.block_solvers.size() >= 2) M.block_solvers.erase(M.block_solvers.begin());
+        M.block_solvers.emplace_back(key, std::shared_ptr<void>(new MultiCore(c, M, AC, method)));
+        slot = M.block_solvers.end() - 1;
     }
-    MultiCore &s = *static_cast<MultiCore *>(M.block_solver.second.get());
+    MultiCore &s = *static_cast<MultiCore *>(slot->second.get());
     int rc = CPK_OK;
     for (int64_t j0 = 0; j0 < k; j0 += kMK) {
         const int kc = (int)std::min<int64_t>(kMK, k - j0);

@@ -168,6 +168,31 @@ int cpk_mat_create_csr(cpk_ctx ctx, int64_t nrows, int64_t ncols, const int64_t 
 int cpk_mat_destroy(cpk_mat A);
 /* y = A*x on the device (host vectors in/out); replaces MATLAB sparse mtimes A*v. */
 int cpk_mat_spmv(cpk_mat A, const double *x, double *y);
+/* New values with the same sparsity, written into the handle (an interior-point outer iteration:
+ * reg_cpkrylov.m:131 rebuilds opLDL2 from new values once per outer iteration).  val holds the
+ * values in the order of the creating call's value array -- pr of cpk_mat_create_csc, val of
+ * cpk_mat_create_csr, entry 0 being the first entry that call read (pr[jc[0]], val[rowptr[0]]) --
+ * and count is the number of entries it read.  Afterwards A equals, bit for bit, the matrix the
+ * creating call would build from the same index arrays and val (the same column sort, duplicates
+ * summed left to right).  Everything that hangs off the handle stays valid and sees the new
+ * values at its next use: the device copy, the Krylov operators blkdiag(A, C) cached on it, the
+ * solvers cached by a preconditioner with their captured graphs.  A preconditioner built or
+ * refactored from A keeps its own copies: it changes at its next cpk_pc_refactor.  Works on a
+ * host-only matrix.  count == 0 with val == NULL is fine.
+ * Errors, all leaving A as it was: CPK_ERR_ARGS for a NULL handle or NULL val with count > 0,
+ * CPK_ERR_DIM when count differs from the creating call's entry count, CPK_ERR_UNSUPPORTED on a
+ * distributed context. */
+int cpk_mat_set_values(cpk_mat A, const double *val, int64_t count);
+/* The same from device memory, with no host round trip of the values (CPK_ERR_ARGS on a host-only
+ * matrix).  d_val must be complete when the call is made (synchronise the stream that wrote it);
+ * the call blocks: on return d_val may be overwritten or freed.  The handle's host copy is
+ * downloaded again when a host-side reader next needs it (cpk_pc_create, cpk_analyze, the first
+ * blkdiag(A, C) of a pairing). */
+int cpk_mat_set_values_device(cpk_mat A, const double *d_val, int64_t count);
+/* Diagnostic: info[8] = {nrows, ncols, stored entries, entry count of the creating call, values
+ * generation (0 at creation, +1 per successful set), device copy present, Krylov operators
+ * cached on this handle, 0}. */
+int cpk_mat_get_info(cpk_mat A, int64_t info[8]);
 
 /* ---- preconditioner: M = opLDL2(A, B, C), Kp = [A B'; B C] (ops/opLDL2.m:60-92) ------
  * Distributed contexts (nranks > 1): every rank passes the same global matrices; the library
@@ -224,6 +249,10 @@ int cpk_pc_apply_ldl_multi_device(cpk_pc M, int64_t k, const double *d_X, int64_
  * panel solve runs it, info[4] = {columns per panel, kernel launches per panel solve, blocks
  * staged in LDS, blocks on the direct path through global memory} (multi-column sweep). */
 int cpk_pc_multi_info(cpk_pc M, int64_t *info);
+/* Diagnostic: info[4] = {cached single-column solvers, hipGraph instantiations those made so far,
+ * cached block solvers, their instantiations}: a solve that replays cached graphs leaves the
+ * instantiation counts as they were. */
+int cpk_pc_solver_info(cpk_pc M, int64_t info[4]);
 /* Y = M*X for a block of k right-hand sides, DEFINED column by column: column j of Y is what
  * cpk_pc_apply returns for column j of X under the current nitref, itref_tol and force_itref, bit
  * for bit -- the reference's double(op), one op*e per column (opLDL2.m:138-149).  (The reference's
