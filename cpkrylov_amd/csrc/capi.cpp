@@ -217,6 +217,39 @@ static void gather_global(Ctx &c, const Precond &p, const double *d_loc, double 
     for (int64_t g = 0; g < dm.N; g++) h_glob[g] = h[(size_t)dm.owner[g] * mx + dm.lidx[g]];
 }
 
+// ---- host arrays of the host-array entries <-> device memory --------------------------------------
+// a host vector of the preconditioner's layout: the rank's slice (or the whole) up, all of it down
+static void stage_up(const Precond &p, const double *h, int64_t len, DBuf<double> &d) {
+    if (p.dist) scatter_global(p, h, len, d);
+    else h2d(d, h, (size_t)len);
+}
+static void stage_down(Ctx &c, const Precond &p, const double *d, double *h) {
+    if (p.dist) {
+        gather_global(c, p, d, h);
+    } else {
+        CPK_HIP(hipMemcpyAsync(h, d, p.N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+    }
+}
+// rows x k of a host block with leading dimension ld, packed on the device (leading dimension
+// ld(): rows, at least 1); the caller's padding rows are never touched
+struct HostBlock {
+    DBuf<double> d;
+    int64_t rows, k;
+    HostBlock(int64_t rows_, int64_t k_) : rows(rows_), k(k_) { d.alloc((size_t)ld() * (size_t)k); }
+    int64_t ld() const { return std::max<int64_t>(rows, 1); }
+    void up(const double *H, int64_t ldh) {
+        if (rows) CPK_HIP(hipMemcpy2D(d.p, ld() * sizeof(double), H, (size_t)ldh * sizeof(double), rows * sizeof(double),
+                                      (size_t)k, hipMemcpyHostToDevice));
+    }
+    // rows [row0, row0 + nrows) of every column (default: all rows)
+    void down(double *H, int64_t ldh, int64_t row0 = 0, int64_t nrows = -1) const {
+        if (nrows < 0) nrows = rows;
+        if (nrows) CPK_HIP(hipMemcpy2D(H, (size_t)ldh * sizeof(double), d.p + row0, ld() * sizeof(double),
+                                       nrows * sizeof(double), (size_t)k, hipMemcpyDeviceToHost));
+    }
+};
+
 extern "C" {
 
 const char *cpk_last_error(void) { return g_err.c_str(); }
@@ -544,16 +577,10 @@ int cpk_pc_apply(cpk_pc M, const double *x, double *y) {
     Precond &p = *M->p;
     Ctx &c = M->ctx->c;
     DBuf<double> dx, dy;
-    if (p.dist) scatter_global(p, x, p.N, dx);
-    else h2d(dx, x, (size_t)p.N);
+    stage_up(p, x, p.N, dx);
     dy.alloc((size_t)std::max<int64_t>(p.N, 1));
     p.apply(dx.p, p.N, dy.p, nullptr);
-    if (p.dist) {
-        gather_global(c, p, dy.p, y);
-    } else {
-        CPK_HIP(hipMemcpyAsync(y, dy.p, p.N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
+    stage_down(c, p, dy.p, y);
     check_chain(p.dF);
     check_chain(p.sep.tsw);
     API_END
@@ -574,16 +601,10 @@ int cpk_pc_apply_ldl(cpk_pc M, const double *x, double *y) {
     Precond &p = *M->p;
     Ctx &c = M->ctx->c;
     DBuf<double> dx, dy;
-    if (p.dist) scatter_global(p, x, p.N, dx);
-    else h2d(dx, x, (size_t)p.N);
+    stage_up(p, x, p.N, dx);
     dy.alloc((size_t)std::max<int64_t>(p.N, 1));
     p.ldl_solve(dx.p, p.N, dy.p, false, nullptr, nullptr);
-    if (p.dist) {
-        gather_global(c, p, dy.p, y);
-    } else {
-        CPK_HIP(hipMemcpyAsync(y, dy.p, p.N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
+    stage_down(c, p, dy.p, y);
     check_chain(p.dF);
     check_chain(p.sep.tsw);
     API_END
@@ -617,14 +638,11 @@ int cpk_pc_apply_ldl_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, do
     Ctx &c = M->ctx->c;
     check_multi(p, k, ldx, ldy);
     if (k == 0 || p.N == 0) return CPK_OK;
-    // packed on the device (leading dimension N); the caller's padding rows are never touched
-    const size_t rowb = (size_t)p.N * sizeof(double);
-    DBuf<double> dX, dY;
-    dX.alloc((size_t)p.N * (size_t)k), dY.alloc((size_t)p.N * (size_t)k);
-    CPK_HIP(hipMemcpy2D(dX.p, rowb, X, (size_t)ldx * sizeof(double), rowb, (size_t)k, hipMemcpyHostToDevice));
-    p.ldl_solve_multi(k, dX.p, p.N, dY.p, p.N);
+    HostBlock dX(p.N, k), dY(p.N, k);
+    dX.up(X, ldx);
+    p.ldl_solve_multi(k, dX.d.p, dX.ld(), dY.d.p, dY.ld());
     CPK_HIP(hipStreamSynchronize(c.stream));
-    CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, rowb, rowb, (size_t)k, hipMemcpyDeviceToHost));
+    dY.down(Y, ldy);
     API_END
 }
 
@@ -660,17 +678,14 @@ int cpk_pc_apply_multi(cpk_pc M, int64_t k, const double *X, int64_t ldx, double
     Ctx &c = M->ctx->c;
     check_apply_multi(p, k, X, ldx, Y, ldy);
     if (k == 0 || p.N == 0) return CPK_OK;
-    // packed on the device (leading dimension N); the caller's padding rows are never touched
-    const size_t rowb = (size_t)p.N * sizeof(double);
-    DBuf<double> dX, dY;
+    HostBlock dX(p.N, k), dY(p.N, k);
     DBuf<int32_t> dn;
-    dX.alloc((size_t)p.N * (size_t)k), dY.alloc((size_t)p.N * (size_t)k);
     if (nit) dn.alloc((size_t)k);
-    CPK_HIP(hipMemcpy2D(dX.p, rowb, X, (size_t)ldx * sizeof(double), rowb, (size_t)k, hipMemcpyHostToDevice));
-    p.apply_multi(k, dX.p, p.N, dY.p, p.N, dn.p);
+    dX.up(X, ldx);
+    p.apply_multi(k, dX.d.p, dX.ld(), dY.d.p, dY.ld(), dn.p);
     CPK_HIP(hipStreamSynchronize(c.stream));
     check_chain(p.dF);
-    CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, rowb, rowb, (size_t)k, hipMemcpyDeviceToHost));
+    dY.down(Y, ldy);
     if (nit) CPK_HIP(hipMemcpy(nit, dn.p, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
     API_END
 }
@@ -700,16 +715,10 @@ int cpk_pc_divide(cpk_pc M, const double *b, double *x) {
     Precond &p = *M->p;
     Ctx &c = M->ctx->c;
     DBuf<double> db, dx;
-    if (p.dist) scatter_global(p, b, p.N, db);
-    else h2d(db, b, (size_t)p.N);
+    stage_up(p, b, p.N, db);
     dx.alloc((size_t)std::max<int64_t>(p.N, 1));
     launch_spmv(c, p.dKp, db.p, dx.p, nullptr);
-    if (p.dist) {
-        gather_global(c, p, dx.p, x);
-    } else {
-        CPK_HIP(hipMemcpyAsync(x, dx.p, p.N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
+    stage_down(c, p, dx.p, x);
     API_END
 }
 
@@ -776,20 +785,14 @@ int cpk_method_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_ma
     const int64_t n = p.n, m = p.m, N = n + m;
     const DMat &AC = A->krylov_op(C, p);
     DBuf<double> db, dxy;
-    if (p.dist) scatter_global(p, b, n, db);
-    else h2d(db, b, (size_t)n);
+    stage_up(p, b, n, db);
     dxy.alloc((size_t)std::max<int64_t>(N, 1));
     auto t0 = std::chrono::steady_clock::now();
     method_solve_device(c, method, db.p, AC, p, opts, dxy.p, stats);
-    if (p.dist) {
-        std::vector<double> g((size_t)p.gN);
-        gather_global(c, p, dxy.p, g.data());
-        std::memcpy(x, g.data(), p.gn * sizeof(double));
-        if (p.gm) std::memcpy(y, g.data() + p.gn, p.gm * sizeof(double));
-    } else {
-        CPK_HIP(hipMemcpy(x, dxy.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (m) CPK_HIP(hipMemcpy(y, dxy.p + n, m * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    std::vector<double> g((size_t)p.gN);  // [x; y], split into the caller's two arrays
+    stage_down(c, p, dxy.p, g.data());
+    std::memcpy(x, g.data(), p.gn * sizeof(double));
+    if (p.gm) std::memcpy(y, g.data() + p.gn, p.gm * sizeof(double));
     if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     API_END
 }
@@ -841,12 +844,7 @@ static void check_solve_multi(cpk_mat A, cpk_mat C, const cpk_pc_s *M, int metho
     if (k < 0 || ld_n[0] < n || ld_n[1] < n || ld_m < m || ld_N[0] < n + m || ld_N[1] < n + m)
         throw Error(CPK_ERR_DIM, "solve_multi: k >= 0 and leading dimensions >= the column length required");
     check_method_dims(A, C, M);
-    const Precond &p = *M->p;
-    if (p.dist || M->ctx->c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
-    if (p.residual_update != 0 && p.handle)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: the handle semantics of residual_update keep one state vector");
-    if (method != CPK_CG && method != CPK_MINRES)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: cpcg and cpminres only (the other methods take one right-hand side)");
+    require_block_solve(M->ctx->c, *M->p, method);
 }
 // the first failing column's status and message, after every column's outputs were written
 static int solve_multi_result(int rc, const std::string &msg) {
@@ -879,21 +877,14 @@ int cpk_method_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *B, 
     if (k == 0) return CPK_OK;
     Ctx &c = ctx->c;
     Precond &p = *M->p;
-    const int64_t n = p.n, m = p.m, N = p.N;
-    // packed on the device; the caller's padding rows are never touched
-    const size_t n1 = (size_t)std::max<int64_t>(n, 1), N1 = (size_t)std::max<int64_t>(N, 1);
-    DBuf<double> dB, dXY;
-    dB.alloc(n1 * (size_t)k), dXY.alloc(N1 * (size_t)k);
-    if (n) CPK_HIP(hipMemcpy2D(dB.p, n1 * sizeof(double), B, (size_t)ldb * sizeof(double), n * sizeof(double), (size_t)k,
-                               hipMemcpyHostToDevice));
+    HostBlock dB(p.n, k), dXY(p.N, k);
+    dB.up(B, ldb);
     auto t0 = std::chrono::steady_clock::now();
     std::string msg;
-    const int rc = method_solve_multi_device(c, method, k, dB.p, (int64_t)n1, A->krylov_op(C, p), p, opts, dXY.p, (int64_t)N1,
+    const int rc = method_solve_multi_device(c, method, k, dB.d.p, dB.ld(), A->krylov_op(C, p), p, opts, dXY.d.p, dXY.ld(),
                                              stats, col_status, &msg);
-    if (n) CPK_HIP(hipMemcpy2D(X, (size_t)ldx * sizeof(double), dXY.p, N1 * sizeof(double), n * sizeof(double), (size_t)k,
-                               hipMemcpyDeviceToHost));
-    if (m) CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dXY.p + n, N1 * sizeof(double), m * sizeof(double), (size_t)k,
-                               hipMemcpyDeviceToHost));
+    dXY.down(X, ldx, 0, p.n);
+    dXY.down(Y, ldy, p.n, p.m);
     const double st = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats)
         for (int64_t j = 0; j < k; j++) stats[j].stime = st;
@@ -926,18 +917,13 @@ int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *Bh, in
     check_solve_multi(A, C, M, method, k, ln, C->h.nrows, lN);
     if (k == 0) return CPK_OK;
     Precond &p = *M->p;
-    const int64_t N = p.N;
-    const size_t N1 = (size_t)std::max<int64_t>(N, 1);
-    DBuf<double> dB, dX;
-    dB.alloc(N1 * (size_t)k), dX.alloc(N1 * (size_t)k);
-    if (N) CPK_HIP(hipMemcpy2D(dB.p, N1 * sizeof(double), Bh, (size_t)ldb * sizeof(double), N * sizeof(double), (size_t)k,
-                               hipMemcpyHostToDevice));
+    HostBlock dB(p.N, k), dX(p.N, k);
+    dB.up(Bh, ldb);
     const ShiftOps so = shift_ops(A, C, p);
     std::string msg;
-    const int rc = reg_solve_multi_device(ctx->c, method, k, dB.p, (int64_t)N1, A->krylov_op(C, p), *so.A, *so.Bt,
-                                          so.bt_colmin, p, opts, dX.p, (int64_t)N1, stats, col_status, &msg);
-    if (N) CPK_HIP(hipMemcpy2D(X, (size_t)ldx * sizeof(double), dX.p, N1 * sizeof(double), N * sizeof(double), (size_t)k,
-                               hipMemcpyDeviceToHost));
+    const int rc = reg_solve_multi_device(ctx->c, method, k, dB.d.p, dB.ld(), A->krylov_op(C, p), *so.A, *so.Bt,
+                                          so.bt_colmin, p, opts, dX.d.p, dX.ld(), stats, col_status, &msg);
+    dX.down(X, ldx);
     return solve_multi_result(rc, msg);
     API_END
 }
@@ -952,14 +938,12 @@ int cpk_debug_spmm(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int64_t k, const
     const int64_t N = p.N;
     if (k < 0 || ldx < N || ldy < N) throw Error(CPK_ERR_DIM, "debug_spmm: k >= 0 and leading dimensions >= N required");
     if (k == 0) return CPK_OK;
-    const size_t N1 = (size_t)std::max<int64_t>(N, 1);
-    DBuf<double> dX, dY, dd;
-    dX.alloc(N1 * (size_t)k), dY.alloc(N1 * (size_t)k), dd.alloc(2 * (size_t)k);
-    if (N) CPK_HIP(hipMemcpy2D(dX.p, N1 * sizeof(double), X, (size_t)ldx * sizeof(double), N * sizeof(double), (size_t)k,
-                               hipMemcpyHostToDevice));
-    debug_spmm(ctx->c, A->krylov_op(C, p), p, k, dX.p, (int64_t)N1, dY.p, (int64_t)N1, dd.p);
-    if (N) CPK_HIP(hipMemcpy2D(Y, (size_t)ldy * sizeof(double), dY.p, N1 * sizeof(double), N * sizeof(double), (size_t)k,
-                               hipMemcpyDeviceToHost));
+    HostBlock dX(N, k), dY(N, k);
+    DBuf<double> dd;
+    dd.alloc(2 * (size_t)k);
+    dX.up(X, ldx);
+    debug_spmm(ctx->c, A->krylov_op(C, p), p, k, dX.d.p, dX.ld(), dY.d.p, dY.ld(), dd.p);
+    dY.down(Y, ldy);
     CPK_HIP(hipMemcpy(dots, dd.p, 2 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }
@@ -973,16 +957,11 @@ int cpk_debug_dot(cpk_ctx ctx, int kind, int64_t n, int nv, const double *A, int
     need(nv == 1 || nv == 2 || nv == 4, "debug_dot: nv is 1, 2 or 4");
     need(n >= 0 && lda >= n && ldb >= n, "debug_dot: n >= 0 and leading dimensions >= n required");
     need(grid >= 0, "debug_dot: grid >= 0 required");
-    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
-    DBuf<double> dA, dB, dd;
-    dA.alloc(n1 * (size_t)nv), dB.alloc(n1 * (size_t)nv), dd.alloc((size_t)nv);
-    if (n) {
-        CPK_HIP(hipMemcpy2D(dA.p, n1 * sizeof(double), A, (size_t)lda * sizeof(double), n * sizeof(double), (size_t)nv,
-                            hipMemcpyHostToDevice));
-        CPK_HIP(hipMemcpy2D(dB.p, n1 * sizeof(double), B, (size_t)ldb * sizeof(double), n * sizeof(double), (size_t)nv,
-                            hipMemcpyHostToDevice));
-    }
-    debug_dot(ctx->c, kind, n, nv, dA.p, (int64_t)n1, dB.p, (int64_t)n1, grid, dd.p);
+    HostBlock dA(n, nv), dB(n, nv);
+    DBuf<double> dd;
+    dd.alloc((size_t)nv);
+    dA.up(A, lda), dB.up(B, ldb);
+    debug_dot(ctx->c, kind, n, nv, dA.d.p, dA.ld(), dB.d.p, dB.ld(), grid, dd.p);
     CPK_HIP(hipMemcpy(out, dd.p, (size_t)nv * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }

@@ -55,42 +55,24 @@ struct Panel {
 template <class F>
 __global__ __launch_bounds__(kBlock) void ew_multi_kernel(int64_t N, Panel<F> p) {
     F f = p.f[blockIdx.y];
-    if (!f.setup()) return;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) f(i);
+    CPK_EW_BODY(N, f);
 }
 template <int NV, class F, class A>
 __global__ __launch_bounds__(kBlock) void ewred_multi_kernel(int64_t N, Panel<F> p, RedBufM rbm) {
     F f = p.f[blockIdx.y];
-    if (!f.setup()) return;
     const RedBuf rb = rbm.col(blockIdx.y);
-    A acc[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) f(i, acc);
-    double tot[NV];
-    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot);
+    CPK_EWRED_BODY(N, f, rb);
 }
 template <class F>
 __global__ __launch_bounds__(kBlock) void ewt_multi_kernel(int64_t N, Panel<F> p) {
     F f = p.f[blockIdx.y];
-    if (!f.setup()) return;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;
-         i0 += (int64_t)gridDim.x * kBlock * kTile)
-        f.tile(i0, N);
+    CPK_EWT_BODY(N, f);
 }
 template <int NV, class F, class A>
 __global__ __launch_bounds__(kBlock) void ewtred_multi_kernel(int64_t N, Panel<F> p, RedBufM rbm) {
     F f = p.f[blockIdx.y];
-    if (!f.setup()) return;
     const RedBuf rb = rbm.col(blockIdx.y);
-    A acc[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;
-         i0 += (int64_t)gridDim.x * kBlock * kTile)
-        f.tile(i0, N, acc);
-    double tot[NV];
-    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot);
+    CPK_EWTRED_BODY(N, f, rb);
 }
 
 // ---- the Krylov product of a panel ---------------------------------------------------------

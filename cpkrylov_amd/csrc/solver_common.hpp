@@ -85,49 +85,63 @@ __device__ __forceinline__ void sym_givens(double a, double b, double &c, double
 #endif
 constexpr int kEwGrid = CPK_EW_GRID;  // fixed grid of the streaming vector kernels (deterministic partials)
 
-// Elementwise kernel over [0, N): F::setup() loads scalars (false => no-op), F::operator()(i).
-template <class F>
-__global__ __launch_bounds__(kBlock) void ew_kernel(int64_t N, F f) {
-    if (!f.setup()) return;
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) f(i);
-}
-
+// The bodies of the element-wise kernels, written once: the single-column kernels below run them
+// on their functor, the panel kernels (multikrylov.hpp) on column blockIdx.y's functor and
+// reduction slice, so a panel column's arithmetic and reduction order are the single column's.
+// Macros on purpose: an inline function is optimised once on its own, the functor behind a
+// pointer, before the kernel is, which cost ewtred_kernel<2, LanczosStep<0>> 6 VGPRs and a wave
+// per SIMD; expanded in place every kernel compiles as before.  NV, A: the enclosing kernel's
+// template parameters; rb: a RedBuf in scope.
+//
+// Elementwise over [0, N): F::setup() loads scalars (false => no-op), F::operator()(i).
+#define CPK_EW_BODY(N, f)                                                                                      \
+    if (!f.setup()) return;                                                                                    \
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) f(i)
 // Elementwise + grid reduction of NV sums: F::operator()(i, acc), F::fin(tot) in the last workgroup.
 // A: the accumulator (double: the default fixed-tree sums; XAcc: exact_dots, xacc.hpp).
-template <int NV, class F, class A = double>
-__global__ __launch_bounds__(kBlock) void ewred_kernel(int64_t N, F f, RedBuf rb) {
-    if (!f.setup()) return;
-    A acc[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) f(i, acc);
-    double tot[NV];
-    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot);
-}
-
+#define CPK_EWRED_BODY(N, f, rb)                                                                               \
+    if (!f.setup()) return;                                                                                    \
+    A acc[NV];                                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);                           \
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock)      \
+        f(i, acc);                                                                                             \
+    double tot[NV];                                                                                            \
+    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot)
 // Tiled forms for the Arnoldi window passes: each thread takes kTile elements per step,
 // kBlock apart (every load coalesced), and F::tile() runs the window loop once for all of them:
 // a window coefficient and basis pointer read from LDS serve kTile elements, and kTile
 // independent chains keep more loads in flight.  Each element's arithmetic is unchanged.
 constexpr int kTile = 4;
+#define CPK_EWT_BODY(N, f)                                                                                     \
+    if (!f.setup()) return;                                                                                    \
+    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;                              \
+         i0 += (int64_t)gridDim.x * kBlock * kTile)                                                            \
+        f.tile(i0, N)
+#define CPK_EWTRED_BODY(N, f, rb)                                                                              \
+    if (!f.setup()) return;                                                                                    \
+    A acc[NV];                                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);                           \
+    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;                              \
+         i0 += (int64_t)gridDim.x * kBlock * kTile)                                                            \
+        f.tile(i0, N, acc);                                                                                    \
+    double tot[NV];                                                                                            \
+    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot)
+
+template <class F>
+__global__ __launch_bounds__(kBlock) void ew_kernel(int64_t N, F f) {
+    CPK_EW_BODY(N, f);
+}
+template <int NV, class F, class A = double>
+__global__ __launch_bounds__(kBlock) void ewred_kernel(int64_t N, F f, RedBuf rb) {
+    CPK_EWRED_BODY(N, f, rb);
+}
 template <class F>
 __global__ __launch_bounds__(kBlock) void ewt_kernel(int64_t N, F f) {
-    if (!f.setup()) return;
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;
-         i0 += (int64_t)gridDim.x * kBlock * kTile)
-        f.tile(i0, N);
+    CPK_EWT_BODY(N, f);
 }
 template <int NV, class F, class A = double>
 __global__ __launch_bounds__(kBlock) void ewtred_kernel(int64_t N, F f, RedBuf rb) {
-    if (!f.setup()) return;
-    A acc[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) acc_init(acc[j], rb.xsub, j, NV);
-    for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kTile + threadIdx.x; i0 < N;
-         i0 += (int64_t)gridDim.x * kBlock * kTile)
-        f.tile(i0, N, acc);
-    double tot[NV];
-    if (grid_sum<NV>(acc, rb, tot) && threadIdx.x == 0) f.fin(tot);
+    CPK_EWTRED_BODY(N, f, rb);
 }
 
 // Single-thread scalar step.
@@ -152,16 +166,17 @@ __global__ void ewred_fin_kernel(F f, const double *tot) {
     if (threadIdx.x || blockIdx.x) return;
     if (f.setup()) f.fin(tot);
 }
-// grid: 0 for the solvers' own ew_grid(N); cpk_debug_dot passes another one (<= kEwGrid)
-template <int NV, class F>
-inline void launch_ewred(Ctx &c, int64_t N, const F &f, int grid = 0) {
-    const int g = grid > 0 ? std::min(grid, kEwGrid) : ew_grid(N);
+// a reducing kernel's launch: its double form or, in exact mode, its XAcc form
+template <class K, class... Args>
+inline void launch_red(Ctx &c, K plain, K exact, dim3 grid, const Args &...args) {
+    hipLaunchKernelGGL(c.exact() ? exact : plain, grid, dim3(kBlock), 0, c.stream, args...);
+}
+// the reducing launch of a single column on a grid of g workgroups, with the distributed epilogue
+template <int NV, class K, class F>
+inline void launch_red_column(Ctx &c, K plain, K exact, int g, int64_t N, const F &f) {
     c.ensure_partials((size_t)g * NV);
     const bool dist = c.dist();
-    if (c.exact())
-        hipLaunchKernelGGL((ewred_kernel<NV, F, XAcc>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
-    else
-        hipLaunchKernelGGL((ewred_kernel<NV, F>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
+    launch_red(c, plain, exact, dim3(g), N, f, red_buf(c));
     if (dist) {
         allreduce_red(c, NV);
         hipLaunchKernelGGL(ewred_fin_kernel<F>, dim3(1), dim3(64), 0, c.stream, f, (const double *)c.red.p);
@@ -173,23 +188,20 @@ inline void launch_ewred(Ctx &c, int64_t N, const F &f, int grid = 0) {
 inline int ewt_grid(int64_t N) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((N + kBlock - 1) / kBlock, CPK_EWT_GRID));
 }
+// grid: 0 for the solvers' own ew_grid(N) / ewt_grid(N); cpk_debug_dot passes another one (<= kEwGrid)
+template <int NV, class F>
+inline void launch_ewred(Ctx &c, int64_t N, const F &f, int grid = 0) {
+    launch_red_column<NV>(c, ewred_kernel<NV, F, double>, ewred_kernel<NV, F, XAcc>,
+                          grid > 0 ? std::min(grid, kEwGrid) : ew_grid(N), N, f);
+}
 template <class F>
 inline void launch_ewt(Ctx &c, int64_t N, const F &f) {
     hipLaunchKernelGGL(ewt_kernel<F>, dim3(ewt_grid(N)), dim3(kBlock), 0, c.stream, N, f);
 }
 template <int NV, class F>
 inline void launch_ewtred(Ctx &c, int64_t N, const F &f, int grid = 0) {
-    const int g = grid > 0 ? std::min(grid, kEwGrid) : ewt_grid(N);
-    c.ensure_partials((size_t)g * NV);
-    const bool dist = c.dist();
-    if (c.exact())
-        hipLaunchKernelGGL((ewtred_kernel<NV, F, XAcc>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
-    else
-        hipLaunchKernelGGL((ewtred_kernel<NV, F>), dim3(g), dim3(kBlock), 0, c.stream, N, f, red_buf(c));
-    if (dist) {
-        allreduce_red(c, NV);
-        hipLaunchKernelGGL(ewred_fin_kernel<F>, dim3(1), dim3(64), 0, c.stream, f, (const double *)c.red.p);
-    }
+    launch_red_column<NV>(c, ewtred_kernel<NV, F, double>, ewtred_kernel<NV, F, XAcc>,
+                          grid > 0 ? std::min(grid, kEwGrid) : ewt_grid(N), N, f);
 }
 template <class F>
 inline void launch_scalar(Ctx &c, const F &f) {

@@ -24,6 +24,7 @@
 #include "solvers.hpp"
 #include "spmv.hpp"
 #include "multikrylov.hpp"
+#include "solve_loop.hpp"
 
 namespace cpk {
 
@@ -1501,54 +1502,36 @@ struct Copy {
 // A SolveCore is kept by the preconditioner between calls with the same method, operators,
 // vectors and captured properties (solver_key): its workspace and the captured iteration
 // graphs are reused, so a repeated solve costs its kernels plus one state upload.
-struct SolveCore {
-    Ctx &c;
+struct SolveCore : SolveDriver {
     Precond &M;
     const DMat &AC;
     int64_t n, m, N;
     int method;
     bool print = true;
-    double atol = 1e-6, rtol = 1e-6, btol = 0, itmax = 0, restart = 50, mem = 50;
-    DBuf<DState> dst;
-    DState h{};
+    double restart = 50, mem = 50;
+    DState &h = hs[0];
     DBuf<double> hist, hist2, hist3, aux, H, cvec, svec, gvec, zvec;
     std::vector<DBuf<double>> vecs;
     int64_t printed = 0;
-    int batch = 16;
-    bool use_graph = true;
     // reused across calls
     std::vector<DBuf<double>> rings;
     size_t ring_next = 0;
-    std::vector<std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // one per loop site
 
     SolveCore(Ctx &cc, Precond &MM, const DMat &ACm, int meth, const cpk_opts *o)
-        : c(cc), M(MM), AC(ACm), n(MM.n), m(MM.m), N(MM.N), method(meth) {
+        : SolveDriver(cc, 1), M(MM), AC(ACm), n(MM.n), m(MM.m), N(MM.N), method(meth) {
         reset(o);
-    }
-    ~SolveCore() {
-        for (auto &g : graphs) {
-            if (g.second) (void)hipGraphExecDestroy(g.second);
-            if (g.first) (void)hipGraphDestroy(g.first);
-        }
     }
     // per-call options (they only reach the device through DState, not through captured kernels)
     void reset(const cpk_opts *o) {
-        // defaults use the global sizes (size(A,1) in the reference), identical on every rank
-        itmax = (method == CPK_GMRES || method == CPK_DQGMRES) ? (double)(M.gn + M.gm) : (double)M.gn;
-        atol = 1e-6, rtol = 1e-6, btol = 0, restart = 50, mem = 50, print = true;
+        resolve(o, (method == CPK_GMRES || method == CPK_DQGMRES) ? (double)(M.gn + M.gm) : (double)M.gn);
+        restart = 50, mem = 50, print = true;
         if (o) {
-            if (o->has_atol) atol = o->atol;
-            if (o->has_rtol) rtol = o->rtol;
-            if (o->has_btol) btol = o->btol;
-            if (o->has_itmax) itmax = o->itmax;
             if (o->has_restart) restart = o->restart;
             if (o->has_mem) mem = std::max(1.0, o->mem);  // cpdqgmres.m:116-118
             if (o->has_print) print = o->print != 0;
         }
-        use_graph = !c.opts.no_graph;
         if (c.dist() && !(c.comm->capturable() && c.opts.dist_graph)) use_graph = false;
         if (c.rank != 0) print = false;
-        batch = c.opts.batch > 0 ? c.opts.batch : 16;
         printed = 0;
         ring_next = 0;
     }
@@ -1574,18 +1557,12 @@ struct SolveCore {
     }
 
     void setup_state(int64_t hcap, int64_t maxv) {
-        ensure(dst, 1);
-        std::memset(&h, 0, sizeof h);
-        h.itmax = (int64_t)std::min(itmax, 9.0e15);
-        if (h.itmax < 0) h.itmax = 0;
-        h.atol = atol, h.rtol = rtol, h.btol = btol;
-        h.hcap = hcap;
-        h.exact = c.exact() ? 1 : 0;
         ensure(hist, hcap);
         ensure(hist2, hcap);
         ensure(hist3, hcap);
         ensure(aux, 3 * hcap);
-        h.hist = hist.p, h.hist2 = hist2.p, h.hist3 = hist3.p, h.aux = aux.p;
+        init_state(h, hcap, hist.p);
+        h.hist2 = hist2.p, h.hist3 = hist3.p, h.aux = aux.p;
         h.restart = (int64_t)restart;
         h.mem = (int64_t)mem;
         if (maxv > 0) {
@@ -1607,11 +1584,6 @@ struct SolveCore {
         need = std::max<size_t>(need, ewg * 2 * std::max<int64_t>(maxv, 1));
         c.ensure_partials(need);
         if (c.exact()) c.ensure_xacc((size_t)std::max<int64_t>(2 * maxv, 4));
-    }
-
-    void pull() {
-        CPK_HIP(hipMemcpyAsync(&h, dst.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
     }
 
     // ---- the distributed solve's status agreement -------------------------------------------
@@ -1665,98 +1637,40 @@ struct SolveCore {
         status_check(local);
     }
 
-    // replay `body` (one iteration) in batches until the device sets `stop`.  A batch is a
-    // captured graph of b iterations (b a power of two <= batch), captured once per loop site
-    // and size and replayed by later calls with the same key.  After the first batch the size
-    // follows the observed convergence rate, so the batch that crosses the tolerance carries
-    // few no-op iterations (every kernel tests the device-side `running` flag, so the size
-    // only affects time, never results).
-    hipGraphExec_t graph_for(size_t site, int b, const std::function<void()> &body) {
-        const size_t slot = site * 8 + (size_t)__builtin_ctz((unsigned)b);
-        if (graphs.size() <= slot) graphs.resize(slot + 1, {nullptr, nullptr});
-        if (!graphs[slot].second) {
-            hipGraph_t graph = nullptr;
-            try {
-                CPK_HIP(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
-                for (int i = 0; i < b; i++) body();
-                CPK_HIP(hipStreamEndCapture(c.stream, &graph));
-                graphs[slot].first = graph;
-                CPK_HIP(hipGraphInstantiate(&graphs[slot].second, graph, nullptr, nullptr, 0));
-                M.graph_inst++;
-            } catch (const Error &e) {
-                // a transport that cannot be captured (deterministic, so every rank lands here):
-                // end the capture, drop the graph and run this solver's batches eagerly
-                hipGraph_t g2 = nullptr;
-                (void)hipStreamEndCapture(c.stream, &g2);
-                if (g2) (void)hipGraphDestroy(g2);
-                if (graph && graph != g2) (void)hipGraphDestroy(graph);
-                graphs[slot] = {nullptr, nullptr};
-                (void)hipGetLastError();
-                if (!c.dist()) throw;
-                fprintf(stderr, "cpk: iteration-graph capture failed (%s); running batches eagerly\n", e.what());
-                use_graph = false;
-                return nullptr;
-            }
+    // what surrounds a batch (run_batches): a rank-local failure of the batch (a host error, a sweep
+    // chain's timed-out wait) joins the batch's status agreement instead of leaving the other ranks
+    // in the next collective (kernels/cpminres.m:195-199: the caller sees the error)
+    template <class L, class R>
+    void agreed_batch(L &&launch, R &&readback) {
+        std::exception_ptr local;
+        int code = 0;
+        try {
+            launch();
+            nbatch++;
+            code = injected("batch", nbatch);
+            if (injected("chain", nbatch) && !debug_set_chain_error(c, M.dF) && !debug_set_chain_error(c, M.sep.tsw))
+                code = CPK_ERR_HIP;  // no chain to fail: the host error instead
+            if (code) throw Error(code, "fail_inject: rank " + std::to_string(c.rank) + " failed after batch " +
+                                            std::to_string(nbatch));
+        } catch (const Error &e) {
+            local = std::current_exception(), code = e.code;
+        } catch (...) {
+            local = std::current_exception(), code = CPK_ERR_HIP;
         }
-        return graphs[slot].second;
+        if (!agreeing()) {
+            if (local) std::rethrow_exception(local);
+        } else {
+            status_enqueue(code);
+        }
+        readback();
+        if (agreeing()) status_check(local);
     }
 
-    static int pow2_at_least(double v, int cap) {
-        int b = 1;
-        while (b < cap && b < v) b <<= 1;
-        return b;
-    }
-
+    // replay `body` (one iteration) in batches until the device sets `stop` (run_batches)
     void loop(const std::function<void()> &body, const std::function<void()> &printer, size_t site = 0) {
-        pull();
-        if (h.stop) return;
-        const int64_t guard = h.k + (int64_t)std::min(itmax, 4.0e9) + 2 * batch + 2;
-        int b = pow2_at_least(batch, 64);
-        const bool adapt = c.opts.batch <= 0;
-        for (;;) {
-            const double res0 = h.residNorm;
-            const int64_t k0 = h.k;
-            // distributed: a rank-local failure of this batch (a host error, a sweep chain's
-            // timed-out wait) joins the batch's status agreement instead of leaving the other
-            // ranks in the next collective (kernels/cpminres.m:195-199: the caller sees the error)
-            std::exception_ptr local;
-            int code = 0;
-            try {
-                hipGraphExec_t exec = use_graph ? graph_for(site, b, body) : nullptr;
-                if (exec) CPK_HIP(hipGraphLaunch(exec, c.stream));
-                else
-                    for (int i = 0; i < b; i++) body();
-                nbatch++;
-                code = injected("batch", nbatch);
-                if (injected("chain", nbatch) && !debug_set_chain_error(c, M.dF) && !debug_set_chain_error(c, M.sep.tsw))
-                    code = CPK_ERR_HIP;  // no chain to fail: the host error instead
-                if (code) throw Error(code, "fail_inject: rank " + std::to_string(c.rank) + " failed after batch " +
-                                                std::to_string(nbatch));
-            } catch (const Error &e) {
-                local = std::current_exception(), code = e.code;
-            } catch (...) {
-                local = std::current_exception(), code = CPK_ERR_HIP;
-            }
-            if (!agreeing()) {
-                if (local) std::rethrow_exception(local);
-            } else {
-                status_enqueue(code);
-            }
-            pull();
-            if (agreeing()) status_check(local);
-            if (print && printer) printer();
-            if (h.stop) break;
-            if (h.k > guard) throw Error(CPK_ERR_HIP, "solver loop did not terminate");
-            b = pow2_at_least(batch, 64);
-            const double res = h.residNorm, tol = h.stopTol;
-            if (adapt && h.k > k0 && res > 0 && res0 > res && tol > 0 && tol < res) {
-                // geometric model of the residual over the last batch: iterations still needed
-                const double rate = std::log(res / res0) / (double)(h.k - k0);
-                const double rem = std::log(tol / res) / rate;
-                if (rem > 0 && rem < 1e6) b = pow2_at_least(std::ceil(rem), b);
-            }
-            if (itmax - (double)h.k < b) b = pow2_at_least(std::max(1.0, itmax - (double)h.k), b);
-        }
+        run_batches(
+            site, 1, M.graph_inst, body, [this](auto &&launch, auto &&readback) { agreed_batch(launch, readback); },
+            print ? printer : nullptr);
     }
 
     std::vector<double> fetch(const DBuf<double> &d, int64_t len) {
@@ -1773,30 +1687,7 @@ struct SolveCore {
         fflush(stdout);
     }
 
-    void raise_error() {
-        char buf[256];
-        if (h.err == 1) {
-            if (method == CPK_CGLANCZOS)
-                snprintf(buf, sizeof buf,
-                         "CPCGLanczos:IndefiniteError: Iter %lld, beta (before sqrt) = %g : preconditioner not second-order sufficient",
-                         (long long)h.err_iter, h.err_val);
-            else
-                snprintf(buf, sizeof buf,
-                         "Iter %lld, beta (before sqrt) = %g : preconditioner does not behave as a spd matrix.",
-                         (long long)h.err_iter, h.err_val);
-        } else if (h.err == 3) {
-            snprintf(buf, sizeof buf,
-                     "Iter 0, 2nd Lanczos vec, beta (before sqrt) = %g : preconditioner does not behave as a spd matrix.",
-                     h.err_val);
-        } else if (h.err == 2) {
-            snprintf(buf, sizeof buf, "Iter %lld, residNorm2 = %g < 0: complex residual norm", (long long)h.err_iter,
-                     h.err_val);
-        } else {
-            snprintf(buf, sizeof buf, "Iter %lld: negative squared norm %g (complex square root)",
-                     (long long)h.err_iter, h.err_val);
-        }
-        throw Error(CPK_ERR_INDEFINITE, buf);
-    }
+    void raise_error() { throw Error(CPK_ERR_INDEFINITE, indefinite_message(method, h)); }
 
     // ------------------------------------------------------------------------------------------
     void minres_like(int kind, const double *b, double *xy, cpk_stats *stats);
@@ -1806,23 +1697,12 @@ struct SolveCore {
 
     void finish_stats(cpk_stats *stats) {
         if (!stats) return;
-        stats->niters = h.k;
-        stats->status = 0;
-        auto cp = [&](double *dstp, const DBuf<double> &src, int64_t len, int64_t *outlen, int prefix, double pv) {
-            *outlen = len + (prefix ? 1 : 0);
-            if (!dstp) return;
-            if (*outlen > stats->hist_cap) throw Error(CPK_ERR_ARGS, "history buffer too small");
-            int64_t off = 0;
-            if (prefix) dstp[0] = pv, off = 1;
-            if (len > 0) CPK_HIP(hipMemcpy(dstp + off, src.p, len * sizeof(double), hipMemcpyDeviceToHost));
-        };
         if (method == CPK_SYMMLQ) {
-            const int prefix = h.flag != 2;  // cgresidHistory = [beta1; cgresidHistory]
-            cp(stats->hist, hist, std::min(h.nh, h.hcap), &stats->hist_len, prefix, h.beta1);
-            cp(stats->hist_lq, hist2, std::min(h.nh2, h.hcap), &stats->lq_len, 0, 0);
-            cp(stats->hist_qr, hist3, std::min(h.nh3, h.hcap), &stats->qr_len, 0, 0);
+            fill_stats(*stats, h, h.flag != 2, h.beta1);  // cgresidHistory = [beta1; cgresidHistory]
+            copy_history(*stats, stats->hist_lq, hist2.p, std::min(h.nh2, h.hcap), &stats->lq_len);
+            copy_history(*stats, stats->hist_qr, hist3.p, std::min(h.nh3, h.hcap), &stats->qr_len);
         } else {
-            cp(stats->hist, hist, std::min(h.nh, h.hcap), &stats->hist_len, 0, 0);
+            fill_stats(*stats, h);
             stats->lq_len = stats->qr_len = 0;
         }
     }
@@ -1830,7 +1710,7 @@ struct SolveCore {
 
 // ---- cpminres / cpcglanczos / cpsymmlq ------------------------------------------------------
 void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *stats) {
-    const int64_t hcap = (int64_t)std::min(itmax, 1.0e8) + 4;
+    const int64_t hcap = hist_capacity(itmax);
     setup_state(hcap, 0);
     DState *st = dst.p;
     double *VQ = ring(3);  // Lanczos vectors [vk; qk] for k-1, k, k+1
@@ -1993,7 +1873,7 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
 
 // ---- cpcg -------------------------------------------------------------------------------------
 void SolveCore::cg(const double *b, double *xy, cpk_stats *stats) {
-    const int64_t hcap = (int64_t)std::min(itmax, 1.0e8) + 4;
+    const int64_t hcap = hist_capacity(itmax);
     setup_state(hcap, 0);
     DState *st = dst.p;
     double *GW = vec(0), *PQ = vec(1), *APCQ = vec(2), *RU = vec(3), *TT = vec(4);
@@ -2104,7 +1984,7 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
     const double memd = std::min(mem, itmax);  // cpdqgmres.m:125
     mem = std::max(1.0, memd);
     const int64_t Mm = (int64_t)mem, M1 = Mm + 1;
-    const int64_t hcap = (int64_t)std::min(itmax, 1.0e8) + 4;
+    const int64_t hcap = hist_capacity(itmax);
     setup_state(hcap, Mm);
     DState *st = dst.p;
     double *V = ring((size_t)M1), *PV = ring((size_t)M1);
@@ -2301,497 +2181,11 @@ void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, con
     if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// the panel product alone (cpk_debug_spmm): no solver state is read or written but `running`
-struct PolDebugSpmm {
-    const double *X;
-    double *out;
-    __device__ const double *select(DState *, const double *) { return X; }
-    __device__ void fin(DState *, const double *tot) { out[0] = tot[0], out[1] = tot[1]; }
-};
+}  // namespace cpk
 
-// ==============================================================================================
-// The lockstep block solve (cpk_method_solve_multi): kc <= kMultiKP columns of cpcg / cpminres
-// iterate together, one Krylov product for the panel (spmm_krylov_kernel), one panel apply of M
-// (Precond::apply_multi) and one launch per element-wise pass (multikrylov.hpp) per iteration.
-// Defined column by column: column j is kernels/cpcg.m / kernels/cpminres.m on b(:, j), with its
-// own DState (stop test, history, error), so a column that stops freezes while the others run on.
-// cpminres runs the unfused sequence (engine option no_minres_fuse): product, M*z, LanczosStep<0>,
-// MinresUpdate.  The solver's vectors are N x kMultiKP column-major blocks (leading dimension N),
-// the layout apply_multi takes; [x; y] is kept in the solver's own block and copied out at the
-// end, so the captured graphs do not depend on the caller's pointers.
-struct MultiCore {
-    Ctx &c;
-    Precond &M;
-    const DMat &AC;
-    int64_t n, m, N;
-    int method;
-    double atol = 1e-6, rtol = 1e-6, itmax = 0;
-    int batch = 16;
-    bool use_graph = true;
-    DBuf<DState> dst;
-    DState h[kMK];
-    DBuf<double> hist;
-    int64_t hcap = 0;
-    std::vector<DBuf<double>> vecs;
-    DBuf<double> parts, spart;
-    DBuf<unsigned> counters;
-    DBuf<int64_t> xsub;
-    DBuf<int> any;
-    size_t pstride = 0;
-    std::map<std::pair<int, int>, std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // (kc, batch)
+#include "multisolve.hpp"  // the block solve's host side, on the functors and the driver above
 
-    MultiCore(Ctx &cc, Precond &MM, const DMat &ACm, int meth) : c(cc), M(MM), AC(ACm), n(MM.n), m(MM.m), N(MM.N), method(meth) {
-        dst.alloc(kMK);
-        any.alloc(1);
-        pstride = (size_t)std::max<int64_t>(kEwGrid, ewt_grid(N)) * 2;
-        parts.alloc(pstride * kMK);
-        counters.alloc((size_t)(kMK + 1) * kTicketWords);
-        CPK_HIP(hipMemset(counters.p, 0, counters.bytes()));
-        if (c.exact()) {
-            xsub.alloc(kMultiXStride * kMK);
-            CPK_HIP(hipMemset(xsub.p, 0, xsub.bytes()));  // the launches leave them zero
-        }
-    }
-    ~MultiCore() {
-        for (auto &g : graphs) {
-            if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
-            if (g.second.first) (void)hipGraphDestroy(g.second.first);
-        }
-    }
-    // block i: `cols` N-vectors per column, column j's at block(i, cols) + j * cols * N
-    double *block(size_t i, size_t cols = 1) {
-        while (vecs.size() <= i) vecs.emplace_back();
-        const size_t want = std::max<size_t>(cols * (size_t)N * kMK, 1);
-        if (vecs[i].n != want) vecs[i].alloc(want);
-        return vecs[i].p;
-    }
-    RedBufM rbm() const { return RedBufM{parts.p, pstride, counters.p, xsub.p}; }
-
-    // history: the panel's kc columns only, itmax + 4 entries each (the single-column solver's
-    // capacity per column); none for the diagnostics, whose columns record nothing
-    void reset(const cpk_opts *o, int kc, bool history = true) {
-        itmax = (double)M.gn, atol = 1e-6, rtol = 1e-6;
-        if (o) {
-            if (o->has_atol) atol = o->atol;
-            if (o->has_rtol) rtol = o->rtol;
-            if (o->has_itmax) itmax = o->itmax;
-        }
-        use_graph = !c.opts.no_graph;
-        batch = c.opts.batch > 0 ? c.opts.batch : 16;
-        hcap = history ? (int64_t)std::min(itmax, 1.0e8) + 4 : 0;
-        if (hist.n < (size_t)hcap * kc) hist.alloc((size_t)hcap * kc);
-        for (int j = 0; j < kMK; j++) {
-            std::memset(&h[j], 0, sizeof h[j]);
-            h[j].itmax = (int64_t)std::min(itmax, 9.0e15);
-            if (h[j].itmax < 0) h[j].itmax = 0;
-            h[j].atol = atol, h[j].rtol = rtol;
-            h[j].exact = c.exact() ? 1 : 0;
-            if (j < kc && hcap > 0) h[j].hcap = hcap, h[j].hist = hist.p + (size_t)j * hcap;
-            if (j >= kc) h[j].stop = 1;  // a padding column never runs (and has no history)
-        }
-        CPK_HIP(hipMemcpyAsync(dst.p, h, sizeof h, hipMemcpyHostToDevice, c.stream));
-    }
-    void pull() {
-        CPK_HIP(hipMemcpyAsync(h, dst.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
-
-    template <class F, class Mk>
-    static Panel<F> panel_of(int kc, const Mk &mk) {
-        Panel<F> p{};
-        for (int j = 0; j < kMK; j++) p.f[j] = mk(j < kc ? j : 0);  // the padding entries are never launched
-        return p;
-    }
-    template <class F>
-    void ew(int kc, const Panel<F> &p) {
-        hipLaunchKernelGGL(ew_multi_kernel<F>, dim3(ew_grid(N), kc), dim3(kBlock), 0, c.stream, N, p);
-    }
-    template <class F>
-    void ewt(int kc, const Panel<F> &p) {
-        hipLaunchKernelGGL(ewt_multi_kernel<F>, dim3(ewt_grid(N), kc), dim3(kBlock), 0, c.stream, N, p);
-    }
-    template <int NV, class F>
-    void ewred(int kc, const Panel<F> &p) {
-        if (c.exact())
-            hipLaunchKernelGGL((ewred_multi_kernel<NV, F, XAcc>), dim3(ew_grid(N), kc), dim3(kBlock), 0, c.stream, N, p, rbm());
-        else
-            hipLaunchKernelGGL((ewred_multi_kernel<NV, F, double>), dim3(ew_grid(N), kc), dim3(kBlock), 0, c.stream, N, p, rbm());
-    }
-    template <int NV, class F>
-    void ewtred(int kc, const Panel<F> &p) {
-        if (c.exact())
-            hipLaunchKernelGGL((ewtred_multi_kernel<NV, F, XAcc>), dim3(ewt_grid(N), kc), dim3(kBlock), 0, c.stream, N, p, rbm());
-        else
-            hipLaunchKernelGGL((ewtred_multi_kernel<NV, F, double>), dim3(ewt_grid(N), kc), dim3(kBlock), 0, c.stream, N, p, rbm());
-    }
-    // the resident grid of the product (occupancy x CUs), as spmv_grid: no trailing partial wave
-    // of workgroups, and a fixed grid fixes which partials a column's inner products sum
-    template <class Pol, class A>
-    unsigned spmm_grid() {
-        static const int64_t resident = [] {
-            int occ = 0, dev = 0, cus = 256;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)spmm_krylov_kernel<Pol, A>, kBlock, 0) != hipSuccess ||
-                occ < 1)
-                occ = 1;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            return (int64_t)occ * cus;
-        }();
-        return (unsigned)std::max<int64_t>(1, std::min<int64_t>(AC.nblk, resident));
-    }
-    // before any capture: the occupancy query and the product's partials
-    template <class Pol>
-    void spmm_prepare() {
-        const unsigned g = c.exact() ? spmm_grid<Pol, XAcc>() : spmm_grid<Pol, double>();
-        if (spart.n < (size_t)g * kMK * 2) spart.alloc((size_t)g * kMK * 2);
-    }
-    template <class Pol, class A>
-    void spmm_as(int kc, const Panel<Pol> &p, double *Y, double *Ys) {
-        const unsigned g = spmm_grid<Pol, A>();
-        hipLaunchKernelGGL((spmm_krylov_kernel<Pol, A>), dim3(g), dim3(kBlock), 0, c.stream, AC.ptr.p, AC.col.p, AC.val.p,
-                           AC.blk.p, AC.nblk, dst.p, kc, p, Y, N, Ys, n, spart.p, rbm(), any.p);
-    }
-    template <class Pol>
-    void spmm(int kc, const Panel<Pol> &p, double *Y, double *Ys) {
-        if (c.exact()) spmm_as<Pol, XAcc>(kc, p, Y, Ys);
-        else spmm_as<Pol, double>(kc, p, Y, Ys);
-    }
-    // M * z for the panel inside the loop: nothing runs when no column does, and a column that
-    // goes through the single-column apply tests its own `running`
-    void mapply(int kc, const double *X, double *Y, bool gated) {
-        const int *run = &dst.p->running;
-        M.apply_multi(kc, X, N, Y, N, nullptr, gated ? any.p : nullptr, gated ? run : nullptr, sizeof(DState) / sizeof(int));
-    }
-
-    hipGraphExec_t graph_for(int kc, int b, const std::function<void()> &body) {
-        auto &slot = graphs[{kc, b}];
-        if (!slot.second) {
-            hipGraph_t graph = nullptr;
-            try {
-                CPK_HIP(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
-                for (int i = 0; i < b; i++) body();
-                CPK_HIP(hipStreamEndCapture(c.stream, &graph));
-                slot.first = graph;
-                CPK_HIP(hipGraphInstantiate(&slot.second, graph, nullptr, nullptr, 0));
-                M.block_graph_inst++;
-            } catch (const Error &) {
-                hipGraph_t g2 = nullptr;
-                (void)hipStreamEndCapture(c.stream, &g2);
-                if (g2) (void)hipGraphDestroy(g2);
-                if (graph && graph != g2) (void)hipGraphDestroy(graph);
-                slot = {nullptr, nullptr};
-                (void)hipGetLastError();
-                throw;
-            }
-        }
-        return slot.second;
-    }
-
-    // SolveCore::loop for a panel: graph batches of b iterations, the kc states read back between
-    // batches; ends when every column's stop is set, and the adaptive batch size follows the
-    // slowest column still running (the size only affects time: every kernel tests `running`)
-    void loop(int kc, const std::function<void()> &body) {
-        pull();
-        auto done = [&] {
-            for (int j = 0; j < kc; j++)
-                if (!h[j].stop) return false;
-            return true;
-        };
-        if (done()) return;
-        const int64_t guard = (int64_t)std::min(itmax, 4.0e9) + 2 * batch + 2;
-        const int base = SolveCore::pow2_at_least(batch, 64);
-        int b = base;
-        const bool adapt = c.opts.batch <= 0;
-        for (;;) {
-            double res0[kMK];
-            int64_t k0[kMK];
-            for (int j = 0; j < kc; j++) res0[j] = h[j].residNorm, k0[j] = h[j].k;
-            hipGraphExec_t exec = use_graph ? graph_for(kc, b, body) : nullptr;
-            if (exec) CPK_HIP(hipGraphLaunch(exec, c.stream));
-            else
-                for (int i = 0; i < b; i++) body();
-            CPK_HIP(hipGetLastError());
-            pull();
-            if (done()) break;
-            int want = 1;
-            double left = 1;
-            for (int j = 0; j < kc; j++) {
-                if (h[j].stop) continue;
-                if (h[j].k > guard) throw Error(CPK_ERR_HIP, "solver loop did not terminate");
-                int bj = base;
-                const double res = h[j].residNorm, tol = h[j].stopTol;
-                if (adapt && h[j].k > k0[j] && res > 0 && res0[j] > res && tol > 0 && tol < res) {
-                    const double rate = std::log(res / res0[j]) / (double)(h[j].k - k0[j]);
-                    const double rem = std::log(tol / res) / rate;
-                    if (rem > 0 && rem < 1e6) bj = SolveCore::pow2_at_least(std::ceil(rem), bj);
-                }
-                want = std::max(want, bj);
-                left = std::max(left, itmax - (double)h[j].k);
-            }
-            b = want;
-            if (left < b) b = SolveCore::pow2_at_least(left, b);
-        }
-    }
-
-    void cg(int kc, const double *B, int64_t ldb);
-    void minres(int kc, const double *B, int64_t ldb);
-    double panel_bytes(int kc) const;
-};
-
-// cpcg.m:126-192 for every column of the panel
-void MultiCore::cg(int kc, const double *B, int64_t ldb) {
-    DState *st = dst.p;
-    double *GW = block(0), *PQ = block(1), *APCQ = block(2), *RU = block(3), *TT = block(4), *XA = block(5);
-    const int64_t N_ = N, n_ = n;
-    ew(kc, panel_of<CgInit0>(kc, [&](int j) { return CgInit0{B + j * ldb, GW + j * N_, XA + j * N_, n_}; }));
-    mapply(kc, GW, RU, false);
-    ewred<1>(kc, panel_of<CgInit1>(kc, [&](int j) { return CgInit1{st + j, RU + j * N_, GW + j * N_, PQ + j * N_, n_}; }));
-    CPK_HIP(hipGetLastError());
-    const auto pol = panel_of<PolCgSpmv>(kc, [&](int j) { return PolCgSpmv{PQ + j * N_}; });
-    const auto step = panel_of<CgStep>(kc, [&](int j) { return CgStep{st + j, XA + j * N_, GW + j * N_, PQ + j * N_, APCQ + j * N_, 0.0}; });
-    const auto resid = panel_of<CgResid>(kc, [&](int j) { return CgResid{st + j, XA + j * N_, RU + j * N_, GW + j * N_, TT + j * N_, n_}; });
-    const auto dir = panel_of<CgDir>(kc, [&](int j) { return CgDir{st + j, RU + j * N_, TT + j * N_, PQ + j * N_, n_, 0.0}; });
-    spmm_prepare<PolCgSpmv>();
-    auto body = [&]() {
-        spmm(kc, pol, APCQ, nullptr);
-        ew(kc, step);
-        mapply(kc, GW, RU, true);
-        ewred<2>(kc, resid);
-        ew(kc, dir);
-    };
-    loop(kc, body);
-}
-
-// cpminres.m:141-252 for every column of the panel
-void MultiCore::minres(int kc, const double *B, int64_t ldb) {
-    DState *st = dst.p;
-    double *VQ = block(0, 3), *W = block(1, 3);  // per column: the three Lanczos slots, the three w slots
-    double *UT = block(2), *UTS = block(3), *VPREC = block(4), *XY = block(5);
-    const int64_t N_ = N, n_ = n;
-    for (int j = 0; j < kc; j++) launch_set_concat(c, UT + j * N_, B + j * ldb, n, m);  // [u; t] = [b; 0]
-    mapply(kc, UT, VPREC, false);
-    ewred<1>(kc, panel_of<InitLanczos<0>>(kc, [&](int j) {
-                 double *v = VQ + j * 3 * N_, *w = W + j * 3 * N_;
-                 return InitLanczos<0>{st + j, VPREC + j * N_, B + j * ldb, v + N_, v, w + 2 * N_, XY + j * N_, n_};
-             }));
-    ew(kc, panel_of<NormalizeCopy>(kc, [&](int j) { return NormalizeCopy{st + j, VQ + j * 3 * N_ + N_, W + j * 3 * N_, 0, 0.0}; }));
-    CPK_HIP(hipGetLastError());
-    const auto pol = panel_of<PolLanczosSpmv<0>>(kc, [&](int j) { return PolLanczosSpmv<0>{VQ + j * 3 * N_, N_, 0}; });
-    const auto ls = panel_of<LanczosStep<0>>(kc, [&](int j) {
-        return LanczosStep<0>{st + j, VQ + j * 3 * N_, VPREC + j * N_, UT + j * N_, XY + j * N_, W + j * 3 * N_, n_, N_, 0, 2, 1};
-    });
-    const auto upd = panel_of<MinresUpdate>(kc, [&](int j) { return MinresUpdate{st + j, VQ + j * 3 * N_, W + j * 3 * N_, XY + j * N_, n_, N_}; });
-    spmm_prepare<PolLanczosSpmv<0>>();
-    auto body = [&]() {
-        spmm(kc, pol, UT, UTS);      // u = A*vk; t = C*qk; alpha; and [u; -t]
-        mapply(kc, UTS, VPREC, true);  // vprec = M * [u; -t]
-        ewtred<2>(kc, ls);
-        ewt(kc, upd);
-    };
-    loop(kc, body);
-}
-
-// Algorithmic HBM bytes of one iteration of a panel of kc columns (DESIGN.md "Lockstep block
-// solve"): blkdiag(A, C) once, the panel apply once, the vector passes per column
-double MultiCore::panel_bytes(int kc) const {
-    const double Nn = (double)N, l = (double)M.dF.nnz, KP = kMK;
-    const double spmm = 12.0 * AC.nnz + 4.0 * (Nn + 1) + kc * 16.0 * Nn + (method == CPK_MINRES ? kc * 8.0 * Nn : 0.0);
-    double mapply;
-    if (kc < kApplyMultiMinCols && !M.multi_panel) {
-        mapply = kc * M.apply_bytes();
-    } else {
-        const double steps = M.nitref > 0 ? M.nitref : 0;
-        const double sweep = 12.0 * l + 4.0 * (Nn + 1) + 4.0 * Nn + KP * 16.0 * Nn;  // L once, the panel in and out
-        const double resid = 12.0 * (double)M.dKp.nnz + 4.0 * (Nn + 1) + kc * 8.0 * Nn + KP * 16.0 * Nn;
-        mapply = 2 * (1 + steps) * sweep + steps * resid + (KP + kc) * 8.0 * Nn;
-    }
-    const double vec = kc * 8.0 * Nn * (method == CPK_MINRES ? 5 + 8 : 6 + 5 + 4);
-    return spmm + mapply + vec;
-}
-
-static std::string block_key(const Ctx &c, const Precond &M, const DMat &AC, int method) {
-    char buf[512];
-    snprintf(buf, sizeof buf, "%d|%llu|%p|%p|%p|%.17g|%.17g|%.17g|%d|%d|%llx", method, (unsigned long long)AC.gen,
-             (const void *)c.partials.p, (const void *)c.counter.p, (const void *)c.xsub.p, M.nitref, M.force_itref,
-             M.itref_tol, (M.residual_update != 0 && M.handle) ? 1 : 0, M.multi_panel ? 1 : 0,
-             (unsigned long long)engine_opts_hash(c.opts));
-    return buf;
-}
-
-int method_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int64_t ldb, const DMat &AC, Precond &M,
-                              const cpk_opts *opts, double *d_XY, int64_t ldxy, cpk_stats *stats, int *col_status,
-                              std::string *errmsg) {
-    if (M.dist || c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
-    if (M.residual_update != 0 && M.handle)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: the handle semantics of residual_update keep one state vector");
-    if (method != CPK_CG && method != CPK_MINRES)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: cpcg and cpminres only");
-    if (k <= 0) return CPK_OK;
-    // the reduction workspace of the single-column applies a short panel loops over, sized before
-    // any capture (it keys the captured graphs)
-    c.ensure_partials(std::max<size_t>((size_t)std::max<int64_t>(AC.nblk, M.dKp.nblk) * 2, (size_t)kEwGrid * 2));
-    const std::string key = block_key(c, M, AC, method);
-    // one per block method (cpcg, cpminres), so an outer loop that runs both on new values keeps
-    // replaying both sets of graphs; a third key (other properties or options) drops the oldest
-    auto slot = M.block_solvers.begin();
-    while (slot != M.block_solvers.end() && slot->first != key) ++slot;
-    if (slot == M.block_solvers.end()) {
-        if (M.block_solvers.size() >= 2) M.block_solvers.erase(M.block_solvers.begin());
-        M.block_solvers.emplace_back(key, std::shared_ptr<void>(new MultiCore(c, M, AC, method)));
-        slot = M.block_solvers.end() - 1;
-    }
-    MultiCore &s = *static_cast<MultiCore *>(slot->second.get());
-    int rc = CPK_OK;
-    for (int64_t j0 = 0; j0 < k; j0 += kMK) {
-        const int kc = (int)std::min<int64_t>(kMK, k - j0);
-        CPK_HIP(hipEventRecord(c.ev0, c.stream));
-        s.reset(opts, kc);
-        if (method == CPK_CG) s.cg(kc, d_B + j0 * ldb, ldb);
-        else s.minres(kc, d_B + j0 * ldb, ldb);
-        if (s.N > 0)
-            CPK_HIP(hipMemcpy2DAsync(d_XY + j0 * ldxy, (size_t)ldxy * sizeof(double), s.block(5), (size_t)s.N * sizeof(double),
-                                     (size_t)s.N * sizeof(double), (size_t)kc, hipMemcpyDeviceToDevice, c.stream));
-        CPK_HIP(hipEventRecord(c.ev1, c.stream));
-        CPK_HIP(hipEventSynchronize(c.ev1));
-        check_chain(M.dF);
-        float ms = 0;
-        CPK_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        int64_t iters = 0;
-        for (int j = 0; j < kc; j++) iters = std::max(iters, s.h[j].k);
-        const double bytes = (double)iters * s.panel_bytes(kc) / kc;
-        for (int j = 0; j < kc; j++) {
-            const DState &h = s.h[j];
-            int code = CPK_OK;
-            if (h.err) {
-                code = CPK_ERR_INDEFINITE;
-                if (rc == CPK_OK) {
-                    rc = code;
-                    char buf[256];
-                    if (h.err == 1)
-                        snprintf(buf, sizeof buf,
-                                 "column %lld: Iter %lld, beta (before sqrt) = %g : preconditioner does not behave as a spd matrix.",
-                                 (long long)(j0 + j), (long long)h.err_iter, h.err_val);
-                    else
-                        snprintf(buf, sizeof buf, "column %lld: Iter %lld, residNorm2 = %g < 0: complex residual norm",
-                                 (long long)(j0 + j), (long long)h.err_iter, h.err_val);
-                    if (errmsg) *errmsg = buf;
-                }
-            }
-            if (col_status) col_status[j0 + j] = code;
-            if (!stats) continue;
-            cpk_stats &o = stats[j0 + j];
-            o.niters = h.k;
-            o.status = 0;
-            o.solved = !h.err && h.residNorm <= h.stopTol;
-            o.lq_len = o.qr_len = 0;
-            o.hist_len = std::min(h.nh, h.hcap);
-            o.loop_ms = ms;
-            o.bytes_moved = bytes;
-            if (o.hist) {
-                if (o.hist_len > o.hist_cap) throw Error(CPK_ERR_ARGS, "history buffer too small");
-                if (o.hist_len > 0)
-                    CPK_HIP(hipMemcpy(o.hist, h.hist, o.hist_len * sizeof(double), hipMemcpyDeviceToHost));
-            }
-        }
-    }
-    return rc;
-}
-
-// reg_cpkrylov.m:152-175 for every column of an N x k block with an existing M: the shift is
-// decided per column by any(b(n+1:N, j)); xy0 = M*[0; b2] of the shifted columns goes through
-// one block apply; b1 and the recovery are formed per column with the single-column kernels.
-// An unshifted column gets xy0 = 0: its solution is the method's, as in reg_solve_device.
-int reg_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int64_t ldb, const DMat &AC,
-                           const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M, const cpk_opts *opts,
-                           double *d_X, int64_t ldx, cpk_stats *stats, int *col_status, std::string *errmsg) {
-    if (M.dist || c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
-    if (M.residual_update != 0 && M.handle)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: the handle semantics of residual_update keep one state vector");
-    if (method != CPK_CG && method != CPK_MINRES)
-        throw Error(CPK_ERR_UNSUPPORTED, "block solve: cpcg and cpminres only");
-    if (k <= 0) return CPK_OK;
-    const int64_t n = M.n, m = M.m, N = M.N;
-    auto t0 = std::chrono::steady_clock::now();
-    const size_t N1 = (size_t)std::max<int64_t>(N, 1), n1 = (size_t)std::max<int64_t>(n, 1);
-    std::vector<int> shift((size_t)k, 0);
-    if (m > 0) {  // any(b(n+1:n+m, j)) per column
-        DBuf<int> flag;
-        flag.alloc((size_t)k);
-        c.ensure_partials((size_t)kEwGrid);
-        CPK_HIP(hipMemsetAsync(flag.p, 0, flag.bytes(), c.stream));
-        for (int64_t j = 0; j < k; j++) launch_ewred<1>(c, m, AnyNonzero{d_B + j * ldb, n, flag.p + j});
-        CPK_HIP(hipMemcpyAsync(shift.data(), flag.p, flag.bytes(), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
-    std::vector<int64_t> sc;  // the shifted columns
-    for (int64_t j = 0; j < k; j++)
-        if (shift[(size_t)j]) sc.push_back(j);
-    const size_t ks = sc.size();
-    DBuf<double> in, xy0, t1, t2, b1, dxy;
-    b1.alloc(n1 * (size_t)k), dxy.alloc(N1 * (size_t)k);
-    if (ks) {
-        in.alloc(N1 * ks), xy0.alloc(N1 * ks), t1.alloc(N1), t2.alloc(N1);
-        // xy0 = M * [zeros(n,1); b(n+1:n+m)]   (reg_cpkrylov.m:156), the shifted columns as one block
-        for (size_t q = 0; q < ks; q++) {
-            if (n) CPK_HIP(hipMemsetAsync(in.p + q * N1, 0, n * sizeof(double), c.stream));
-            CPK_HIP(hipMemcpyAsync(in.p + q * N1 + n, d_B + sc[q] * ldb + n, m * sizeof(double), hipMemcpyDeviceToDevice,
-                                   c.stream));
-        }
-        M.apply_multi((int64_t)ks, in.p, (int64_t)N1, xy0.p, (int64_t)N1, nullptr);
-        for (size_t q = 0; q < ks; q++) {  // b1 = b(1:n) - A*xy0(1:n) - B'*xy0(n+1:N)   (reg_cpkrylov.m:157)
-            launch_spmv(c, Arows, xy0.p + q * N1, t1.p, nullptr);
-            launch_spmv_colmask(c, Btrows, bt_colmin, xy0.p + q * N1, t2.p, nullptr);
-            launch_ew(c, n, ShiftRhs{d_B + sc[q] * ldb, t1.p, t2.p, b1.p + (size_t)sc[q] * n1});
-        }
-    }
-    for (int64_t j = 0; j < k; j++)
-        if (!shift[(size_t)j] && n)
-            CPK_HIP(hipMemcpyAsync(b1.p + (size_t)j * n1, d_B + j * ldb, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-    const int rc = method_solve_multi_device(c, method, k, b1.p, (int64_t)n1, AC, M, opts, dxy.p, (int64_t)N1, stats,
-                                             col_status, errmsg);
-    size_t q = 0;
-    for (int64_t j = 0; j < k; j++) {
-        if (shift[(size_t)j]) {  // x = [xy0(1:n) + dx; xy0(n+1:N) + dy]
-            launch_ew(c, N, Recover{xy0.p + q * N1, dxy.p + (size_t)j * N1, d_X + j * ldx});
-            q++;
-        } else if (N) {
-            CPK_HIP(hipMemcpyAsync(d_X + j * ldx, dxy.p + (size_t)j * N1, N * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-        }
-    }
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    const double st = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats)
-        for (int64_t j = 0; j < k; j++) stats[j].stime = st, stats[j].ptime = M.ptime;
-    return rc;
-}
-
-// Diagnostic (cpk_debug_spmm): the panel product alone, Y(:, j) = blkdiag(A, C) * X(:, j) and the
-// two inner products <y_j(1:n), x_j(1:n)>, <y_j(n+1:N), x_j(n+1:N)> at dots[2 j], dots[2 j + 1]
-void debug_spmm(Ctx &c, const DMat &AC, Precond &M, int64_t k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
-                double *d_dots) {
-    if (M.dist || c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
-    if (k <= 0) return;
-    MultiCore s(c, M, AC, CPK_CG);
-    const int64_t N = s.N;
-    const size_t rowb = (size_t)N * sizeof(double);
-    double *Xb = s.block(0), *Yb = s.block(1);
-    DBuf<double> dots;
-    dots.alloc(2 * kMK);
-    s.spmm_prepare<PolDebugSpmm>();
-    for (int64_t j0 = 0; j0 < k; j0 += kMK) {
-        const int kc = (int)std::min<int64_t>(kMK, k - j0);
-        s.reset(nullptr, kc, false);
-        if (N) CPK_HIP(hipMemcpy2DAsync(Xb, rowb, d_X + j0 * ldx, (size_t)ldx * sizeof(double), rowb, (size_t)kc,
-                                        hipMemcpyDeviceToDevice, c.stream));
-        s.spmm(kc, MultiCore::panel_of<PolDebugSpmm>(kc, [&](int j) { return PolDebugSpmm{Xb + j * N, dots.p + 2 * j}; }), Yb,
-               nullptr);
-        CPK_HIP(hipGetLastError());
-        if (N) CPK_HIP(hipMemcpy2DAsync(d_Y + j0 * ldy, (size_t)ldy * sizeof(double), Yb, rowb, rowb, (size_t)kc,
-                                        hipMemcpyDeviceToDevice, c.stream));
-        CPK_HIP(hipMemcpyAsync(d_dots + 2 * j0, dots.p, (size_t)kc * 2 * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
-}
+namespace cpk {
 
 // Diagnostics (cpk_debug_dot, cpk_debug_xnorm2): the solvers' reductions and the exact mode's
 // norm([a b]) on the caller's values, so the accumulators can be tested at edge values that no
@@ -2852,40 +2246,6 @@ void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, doubl
     CPK_HIP(hipStreamSynchronize(c.stream));
 }
 
-// Diagnostic (cpk_debug_spmm_time): device time per launch (HIP events, `reps` back-to-back
-// launches after a warm-up) of the panel product with kc <= kMultiKP columns and, in the same run,
-// of the single-column Krylov product spmv_stream<EpiKrylov<PolPlainSpmv>> on one column
-void debug_spmm_time(Ctx &c, const DMat &AC, Precond &M, int kc, int reps, double *ms_panel, double *ms_single) {
-    if (M.dist || c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "block solve: single-GPU only");
-    if (kc < 1 || kc > kMK) throw Error(CPK_ERR_DIM, "debug_spmm_time: 1 <= kc <= 8");
-    reps = std::max(reps, 1);
-    MultiCore s(c, M, AC, CPK_CG);
-    const int64_t N = s.N;
-    double *Xb = s.block(0), *Yb = s.block(1);
-    DBuf<double> dots;
-    dots.alloc(2 * kMK);
-    std::vector<double> h((size_t)std::max<int64_t>(N, 1) * kMK);
-    for (size_t i = 0; i < h.size(); i++) h[i] = 1.0 + 1e-3 * (double)(i % 1000);
-    CPK_HIP(hipMemcpy(Xb, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    s.reset(nullptr, kc, false);
-    s.spmm_prepare<PolDebugSpmm>();
-    c.ensure_partials(std::max<size_t>((size_t)AC.nblk * 2, 4096));
-    const auto pol = MultiCore::panel_of<PolDebugSpmm>(kc, [&](int j) { return PolDebugSpmm{Xb + j * N, dots.p + 2 * j}; });
-    auto timeit = [&](const std::function<void()> &f) {
-        f();  // warm
-        CPK_HIP(hipEventRecord(c.ev0, c.stream));
-        for (int r = 0; r < reps; r++) f();
-        CPK_HIP(hipEventRecord(c.ev1, c.stream));
-        CPK_HIP(hipEventSynchronize(c.ev1));
-        float ms = 0;
-        CPK_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        return (double)ms / reps;
-    };
-    *ms_panel = timeit([&]() { s.spmm(kc, pol, Yb, nullptr); });
-    *ms_single = timeit([&]() { launch_krylov_spmv(c, AC, s.dst.p, Yb, s.n, PolPlainSpmv{Xb}); });
-    CPK_HIP(hipGetLastError());
-}
-
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out) {
     const int64_t N = M.N;
     const int64_t NW = std::max<int64_t>(std::max<int64_t>(N, M.nsub + M.sep.nT), 1);  // distributed work vectors
@@ -2896,16 +2256,7 @@ void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *
     std::vector<double> h(NW);
     for (int64_t i = 0; i < NW; i++) h[i] = 1.0 + 1e-3 * (double)(i % 1000);
     CPK_HIP(hipMemcpy(x.p, h.data(), NW * sizeof(double), hipMemcpyHostToDevice));
-    auto timeit = [&](const std::function<void()> &f) {
-        f();  // warm
-        CPK_HIP(hipEventRecord(c.ev0, c.stream));
-        for (int r = 0; r < reps; r++) f();
-        CPK_HIP(hipEventRecord(c.ev1, c.stream));
-        CPK_HIP(hipEventSynchronize(c.ev1));
-        float ms = 0;
-        CPK_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        return (double)ms / reps;
-    };
+    auto timeit = [&](auto &&f) { return time_launches(c, reps, f); };
     const double Nn = (double)N, l = (double)M.dF.nnz;
     out->spmv_ms = timeit([&]() { launch_spmv(c, AC, x.p, y.p, nullptr); });
     out->spmv_bytes = 12.0 * AC.nnz + 4.0 * (Nn + 1) + 8.0 * Nn + 8.0 * Nn;

@@ -17,6 +17,10 @@ int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &B
 // (kernels/cpcg.m, kernels/cpminres.m), panels of kMultiKP columns sharing one Krylov product and
 // one panel apply per iteration.  stats / col_status: k entries or null.  Returns CPK_OK or the
 // status of the first failing column (its message in *errmsg); every column's outputs are written.
+// What the block entries refuse (CPK_ERR_UNSUPPORTED): a distributed context or preconditioner, the
+// handle semantics of residual_update, a method other than cpcg / cpminres.  method < 0: the panel
+// product alone (the diagnostics), which needs the first only.  The callers check before they run.
+void require_block_solve(const Ctx &c, const Precond &M, int method);
 int method_solve_multi_device(Ctx &c, int method, int64_t k, const double *d_B, int64_t ldb, const DMat &AC, Precond &M,
                               const cpk_opts *opts, double *d_XY, int64_t ldxy, cpk_stats *stats, int *col_status,
                               std::string *errmsg);

@@ -440,6 +440,26 @@ def test_indefinite_columns_report_per_column(gpu_ctx, method):
         assert [f["error"] for f in flag] == [_lib.CPK_ERR_INDEFINITE] * 3 and not any(f["solved"] for f in flag)
 
 
+@pytest.mark.parametrize("method", METHODS)
+def test_indefinite_message_is_the_single_columns(gpu_ctx, method):
+    """one formatter writes both texts: the block entry's message for its first failing column is
+    "column 0: " and what the single-column entry raises on that column (exact mode: both stop at
+    the same iteration with the same value)"""
+    import cpkrylov_amd as cpk
+    from cpkrylov_amd import _lib
+    S = ST.tiny_indefinite()
+    Bk = np.asfortranarray(np.column_stack([S["rhs"], 2.0 * S["rhs"], 0.5 * S["rhs"]]))
+    fn = getattr(cpk, "cp" + method)
+    with cpk.engine_options(exact_dots=1):
+        with pytest.raises(cpk.CpkError) as single:
+            cpk.reg_cpkrylov(fn, S["rhs"].copy(), S["Q"], S["B"], S["C"], S["G"], OPTS)
+        with pytest.raises(cpk.CpkError) as blk:
+            cpk.reg_cpkrylov(fn, Bk, S["Q"], S["B"], S["C"], S["G"], OPTS)
+    assert single.value.code == blk.value.code == _lib.CPK_ERR_INDEFINITE
+    print(repr(str(single.value)), repr(str(blk.value)))
+    assert str(blk.value) == "column 0: " + str(single.value)
+
+
 def test_refusals_leave_outputs_untouched(gpu_ctx):
     import cpkrylov_amd as cpk
     from cpkrylov_amd import _lib
