@@ -35,6 +35,12 @@ class Stats(C.Structure):
                 ("loop_ms", C.c_double), ("bytes_moved", C.c_double)]
 
 
+class FactorReport(C.Structure):
+    """cpk_factor_report: what a numeric LDL' phase found (positions are pivot positions)."""
+    _fields_ = [(k, C.c_int64) for k in ("n_pos", "n_neg", "n_wrong", "first_wrong", "n_perturbed", "argmin_abs")] + \
+               [(k, C.c_double) for k in ("min_abs", "max_abs", "max_shift", "pivot_min")]
+
+
 class PcInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n", "m", "N", "nnz_kp", "nnz_l", "nblocks", "nrounds",
                                          "max_block_levels", "depth", "ordering")]
@@ -86,6 +92,10 @@ _SIGS = {
     "cpk_pc_divide": ([vp, P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_pc_get_info": ([vp, P(PcInfo)], C.c_int),
     "cpk_pc_export": ([vp, P(C.c_int64), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_int32)], C.c_int),
+    "cpk_pc_factor_report": ([vp, P(FactorReport)], C.c_int),
+    "cpk_pc_pivot_shift": ([vp, P(C.c_double)], C.c_int),
+    "cpk_analysis_factor_report": ([vp, P(FactorReport)], C.c_int),
+    "cpk_analysis_pivot_shift": ([vp, P(C.c_double)], C.c_int),
     "cpk_analyze": ([vp, vp, vp, C.c_char_p, P(vp)], C.c_int),
     "cpk_analysis_destroy": ([vp], C.c_int),
     "cpk_analysis_get_info": ([vp, P(PcInfo)], C.c_int),

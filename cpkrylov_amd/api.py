@@ -452,10 +452,30 @@ class opLDL2:
         L = sp.csc_matrix((Lx[:nnz], Li[:nnz], Lp), shape=(N, N))
         return L, D, perm
 
+    def factor_report(self):
+        """What the last successful factorization (construction or refactor) found, as a dict of
+        cpk_factor_report's fields: the inertia (n_pos, n_neg) and pivot information MA57's ldl
+        returns with the factors (opLDL2.m:81-82).  Positions index D and perm of
+        export_factors()."""
+        r = _lib.FactorReport()
+        check(lib.cpk_pc_factor_report(self.h, C.byref(r)))
+        return _report_dict(r)
+
+    def pivot_shift(self):
+        """E (N values, original dof order): the factors are those of Kp + diag(E) exactly; zeros
+        unless the engine option pivot_min replaced pivots.  M's Kp stays the unperturbed matrix."""
+        E = np.empty(self.info["N"])
+        check(lib.cpk_pc_pivot_shift(self.h, _dptr(E)))
+        return E
+
     def __del__(self):
         if getattr(self, "h", None):
             lib.cpk_pc_destroy(self.h)
             self.h = None
+
+
+def _report_dict(r):
+    return {k: getattr(r, k) for k, _ in _lib.FactorReport._fields_}
 
 
 class opLDL2Factor:
@@ -548,10 +568,15 @@ def analyze(A, B, Cm, ctx=None, options=None):
         order = np.empty(N, np.int32)
         check(lib.cpk_analysis_schedule(h, None, rp.ctypes.data_as(_P(C.c_int64)), bl.ctypes.data_as(_P(C.c_int64)),
                                         lr.ctypes.data_as(_P(C.c_int64)), order.ctypes.data_as(_P(C.c_int32))))
+        rep = _lib.FactorReport()
+        check(lib.cpk_analysis_factor_report(h, C.byref(rep)))
+        E = np.empty(N)
+        check(lib.cpk_analysis_pivot_shift(h, _dptr(E)))
     finally:
         lib.cpk_analysis_destroy(h)
     L = sp.csc_matrix((Lx[:nnz], Li[:nnz], Lp), shape=(N, N))
-    return dict(info=info, L=L, D=D, perm=perm, round_ptr=rp, blk_lvl=bl, lvl_row=lr, order=order)
+    return dict(info=info, L=L, D=D, perm=perm, round_ptr=rp, blk_lvl=bl, lvl_row=lr, order=order,
+                report=_report_dict(rep), E=E)
 
 
 _PLAN_F64 = {"fsub_Lx", "fsub_D", "extra_val", "tf_val", "tb_val", "DT", "kp_val", "ac_val", "ab_val"}

@@ -755,6 +755,36 @@ int cpk_pc_export(cpk_pc M, int64_t *Lcolptr, int32_t *Lrowind, double *Lval, do
     API_END
 }
 
+static_assert(sizeof(cpk_factor_report) == sizeof(FactorReport), "cpk_factor_report mirrors FactorReport");
+// E in the original dof order from the pivot-order shifts Ek (null: zeros)
+static void shift_to_dofs(const Factor &f, const double *Ek, double *E) {
+    for (int64_t k = 0; k < f.N; k++) E[f.perm[k]] = Ek ? Ek[k] : 0.0;
+}
+
+int cpk_pc_factor_report(cpk_pc M, cpk_factor_report *out) {
+    API_BEGIN
+    need(M && out, "NULL argument");
+    const Precond &p = *M->p;
+    const FactorReport &r = p.dl.ready ? p.dl.rep : p.F.rep;
+    std::memcpy(out, &r, sizeof r);
+    API_END
+}
+
+int cpk_pc_pivot_shift(cpk_pc M, double *E) {
+    API_BEGIN
+    need(M && E, "NULL argument");
+    const Precond &p = *M->p;
+    const Factor &f = p.F;
+    if (p.dl.ready && p.dl.E.n && f.N) {  // shifts computed on the device (ldl.hip), pivot order
+        std::vector<double> ek((size_t)f.N);
+        CPK_HIP(hipMemcpy(ek.data(), p.dl.E.p, (size_t)f.N * sizeof(double), hipMemcpyDeviceToHost));
+        shift_to_dofs(f, ek.data(), E);
+    } else {
+        shift_to_dofs(f, !p.dl.ready && !f.E.empty() ? f.E.data() : nullptr, E);
+    }
+    API_END
+}
+
 static void check_method_dims(cpk_mat A, cpk_mat C, const cpk_pc_s *M) {
     need(A && C && M, "NULL argument");
     if (A->h.nrows != A->h.ncols || C->h.nrows != C->h.ncols) throw Error(CPK_ERR_DIM, "A and C must be square");
@@ -1142,6 +1172,21 @@ int cpk_analysis_export(cpk_analysis a, int64_t *Lcolptr, int32_t *Lrowind, doub
     if (Lval) std::memcpy(Lval, f.Lx.data(), f.Lx.size() * sizeof(double));
     if (D) std::memcpy(D, f.D.data(), f.D.size() * sizeof(double));
     if (perm) std::memcpy(perm, f.perm.data(), f.perm.size() * sizeof(int32_t));
+    API_END
+}
+
+int cpk_analysis_factor_report(cpk_analysis a, cpk_factor_report *out) {
+    API_BEGIN
+    need(a && out, "NULL argument");
+    std::memcpy(out, &a->an.F0.rep, sizeof a->an.F0.rep);
+    API_END
+}
+
+int cpk_analysis_pivot_shift(cpk_analysis a, double *E) {
+    API_BEGIN
+    need(a && E, "NULL argument");
+    const Factor &f = a->an.F0;
+    shift_to_dofs(f, f.E.empty() ? nullptr : f.E.data(), E);
     API_END
 }
 

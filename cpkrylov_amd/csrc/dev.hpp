@@ -100,8 +100,8 @@ struct SweepConfig {
 // (profiles/r04_dist_v3.txt: 815 it/s with the distributed default against 892 on one GPU).
 SweepConfig dist_sweep_default();
 
-// Engine options of a context (opts.cpp; cpk_ctx_set_option).  None changes a result: they
-// select equivalent execution paths (each is tested bit-exact against the default) or the
+// Engine options of a context (opts.cpp; cpk_ctx_set_option).  None but exact_dots and pivot_min
+// changes a result: they select equivalent execution paths (each is tested bit-exact against the default) or the
 // sweep schedule and the distributed split, which every rank must build identically -- so a
 // distributed preconditioner compares a hash of all of them across ranks before its first
 // collective.  A context starts from the CPK_<NAME> environment variables, read once when it
@@ -110,6 +110,8 @@ struct EngineOpts {
     SweepConfig sweep;            // sweep:              LDS staging of the sweep schedule
     bool sweep_set = false;       //                     sweep given explicitly (else the per-path default)
     double split_tol = 0.03;      // split_tol:          distributed subtree weight tolerance
+    double pivot_min = 0;         // pivot_min:          static pivot perturbation: a pivot d of sign s with
+                                  //                     s*d < pivot_min becomes s*pivot_min (0: off; factor.cpp)
     bool host_factor = false;     // host_factor:        numeric LDL' on the host (reference path)
     bool no_pipe = false;         // no_pipe:            round 0 one workgroup per block
     bool no_upper = false;        // no_upper:           upper rounds through the generic kernels
@@ -507,23 +509,37 @@ struct DLdl {
     DBuf<uint32_t> kp_src;
     DBuf<int64_t> kp_from;  // Kp entry -> (block << 40 | entry) of A11 / B / C22 (refactorization)
     DBuf<double> Lx, D, Y;  // L in CSC order, D in pivot order, per-row-entry scratch
-    DBuf<int> bad;
+    DBuf<int64_t> stat;     // word 0: the row kernels' bad[2]; then the report kernel's FactorReport
+    DBuf<int8_t> sgn;       // per pivot position: +1 a dof of the (1,1) block, -1 otherwise
+    // the committed factor's pivot shifts in pivot order (allocated by the first factorization under
+    // pivot_min > 0; empty: zeros) and its report
+    DBuf<double> E;
+    FactorReport rep;
+    DBuf<int64_t> rep_part;  // the report kernel's per-workgroup partials and arrival tickets
+    DBuf<unsigned> rep_ticket;
+    int rep_grid = 1;
     bool sym_ready = false;  // dldl_setup_sym done
     bool ready = false;
 };
 // the two halves of dldl_setup: the symbolic data (uploadable while the host still builds the
 // schedule) and the value sources of the sweep layouts; ready after both
-void dldl_setup_sym(DLdl &d, const LdlSymbolic &sym, const Factor &f);
+// n: the size of the (1,1) block (the pivot signs)
+void dldl_setup_sym(DLdl &d, const LdlSymbolic &sym, const Factor &f, int64_t n);
 void dldl_setup_src(DLdl &d, const std::vector<int32_t> &fsrc, const std::vector<int32_t> &bsrc,
                     const std::vector<int32_t> &order);
-void dldl_setup(DLdl &d, const LdlSymbolic &sym, const Factor &f, const std::vector<int32_t> &fsrc,
+void dldl_setup(DLdl &d, const LdlSymbolic &sym, const Factor &f, int64_t n, const std::vector<int32_t> &fsrc,
                 const std::vector<int32_t> &bsrc, const std::vector<int32_t> &order);
 // numeric factorization from the device Kp values, then DFactor's sweep values and D;
 // throws CPK_ERR_FACTOR on a zero or NaN pivot
 void dldl_factor(Ctx &c, DLdl &d, const double *kpv, DFactor &dF);
-// the numeric phase alone into caller-owned Lx (CSC order) / D (pivot order); throws on a bad
-// pivot having written only Lx, D and d's scratch (a refactorization commits after it returns)
-void dldl_numeric(Ctx &c, DLdl &d, const double *kpv, double *Lx, double *D);
+// the numeric phase alone into caller-owned Lx (CSC order) / D (pivot order) / E (pivot order; the
+// context's pivot_min > 0, else null) and the report of that factor; throws on a bad pivot having
+// written only Lx, D, E and d's scratch (a refactorization commits after it returns)
+void dldl_numeric(Ctx &c, DLdl &d, const double *kpv, double *Lx, double *D, double *E, FactorReport &rep);
+// the same into d's own Lx, D, E and report (a construction)
+void dldl_numeric_own(Ctx &c, DLdl &d, const double *kpv);
+// a refactorization's commit of E (null: none, the committed shifts become zeros) and the report
+void dldl_commit_report(Ctx &c, DLdl &d, const double *E, const FactorReport &rep);
 // DFactor's sweep values and D from d.Lx / d.D
 void dldl_fill(Ctx &c, const DLdl &d, DFactor &dF);
 // Value maps (distributed preconditioner): a device array built from index-valued factor data

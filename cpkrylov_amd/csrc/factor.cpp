@@ -3,6 +3,7 @@
 // triangular sweeps that replace op.LDL = P*inv(L')*inv(D)*inv(L)*P' (ops/opLDL2.m:86).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <atomic>
 #include <cstdlib>
@@ -198,8 +199,31 @@ static Factor ldl_symbolic_threaded(const HCsr &Kp, const std::vector<int32_t> &
 
 static void height_levels(const Factor &f, LdlSymbolic *sym);
 
+FactorReport factor_report(const std::vector<double> &D, const std::vector<int32_t> &perm, int64_t n,
+                           const std::vector<double> &E, double pivot_min) {
+    FactorReport r;
+    r.pivot_min = pivot_min;
+    const int64_t N = (int64_t)D.size();
+    for (int64_t k = 0; k < N; k++) {
+        const double d = D[k], a = std::fabs(d);
+        if (d > 0) r.n_pos++;
+        if (d < 0) r.n_neg++;
+        if ((perm[k] < n ? d : -d) < 0) {
+            if (!r.n_wrong) r.first_wrong = k;
+            r.n_wrong++;
+        }
+        if (k == 0 || a < r.min_abs) r.min_abs = a, r.argmin_abs = k;
+        if (k == 0 || a > r.max_abs) r.max_abs = a;
+        if (!E.empty() && E[k] != 0.0) {
+            r.n_perturbed++;
+            r.max_shift = std::max(r.max_shift, std::fabs(E[k]));
+        }
+    }
+    return r;
+}
+
 Factor ldl_factor(const HCsr &Kp, const std::vector<int32_t> &perm, int /*nthreads*/, LdlSymbolic *sym,
-                  bool numeric) {
+                  bool numeric, double pivot_min, int64_t n) {
     if (!numeric && sym && Kp.nrows > 0) {
         Factor f = ldl_symbolic_threaded(Kp, perm, *sym);
         height_levels(f, sym);
@@ -234,6 +258,8 @@ Factor ldl_factor(const HCsr &Kp, const std::vector<int32_t> &perm, int /*nthrea
     const int64_t nnz = f.Lp[N];
     f.Li.resize(nnz);
     if (numeric) f.Lx.resize(nnz), f.D.resize(N);
+    const bool reg = numeric && pivot_min > 0;
+    if (reg) f.E.assign(N, 0.0);
     if (sym) {
         sym->N = N;
         sym->Rp.assign(N + 1, 0);
@@ -294,11 +320,20 @@ Factor ldl_factor(const HCsr &Kp, const std::vector<int32_t> &perm, int /*nthrea
         }
         if (sym) sym->Rp[k + 1] = (int32_t)rpos;
         if (!numeric) continue;
+        if (reg && d == d) {
+            const bool neg = perm[k] >= n;
+            if ((neg ? -d : d) < pivot_min) {
+                const double dn = neg ? -pivot_min : pivot_min;
+                f.E[k] = dn - d;
+                d = dn;
+            }
+        }
         if (d == 0.0 || !(d == d))
             throw Error(CPK_ERR_FACTOR, "ldl: zero or NaN pivot at position " + std::to_string(k) +
                                             " (static 1x1 pivoting needs G > 0 on the nullspace and C > 0)");
         f.D[k] = d;
     }
+    if (numeric) f.rep = factor_report(f.D, perm, n, f.E, pivot_min);
     if (sym) height_levels(f, sym);
     return f;
 }

@@ -103,6 +103,23 @@ std::vector<int32_t> min_degree(const HCsr &graph);
 std::vector<int32_t> nested_dissection(const HCsr &graph, int leaf_size);
 
 // ---- factorization -----------------------------------------------------------------------
+// What a numeric phase reports about its factor (the C ABI's cpk_factor_report, field for field):
+// the inertia and pivot information MA57's ldl returns with the factors (opLDL2.m:81-82).
+// Positions are pivot positions (the index into D and perm).
+struct FactorReport {
+    int64_t n_pos = 0, n_neg = 0;  // signs of D = the inertia of the factored matrix (Sylvester)
+    int64_t n_wrong = 0;           // pivots with s_k * d < 0 (s_k: see ldl_factor)
+    int64_t first_wrong = -1;      // the lowest such position
+    int64_t n_perturbed = 0;       // pivots replaced under pivot_min (E_k != 0)
+    int64_t argmin_abs = -1;       // position of min |d|, the lowest on ties
+    double min_abs = 0, max_abs = 0;
+    double max_shift = 0;          // max |E_k|
+    double pivot_min = 0;          // the option's value at this factorization
+};
+// the report of a finished factor: D and E (empty: zeros) in pivot order, n = size of the (1,1) block
+FactorReport factor_report(const std::vector<double> &D, const std::vector<int32_t> &perm, int64_t n,
+                           const std::vector<double> &E, double pivot_min);
+
 // P'*Kp*P = L*D*L', L unit lower (strict part stored), D diagonal (1x1 static pivots).
 struct Factor {
     int64_t N = 0;
@@ -112,6 +129,10 @@ struct Factor {
     std::vector<double> Lx;
     std::vector<double> D;
     std::vector<int32_t> parent; // elimination tree
+    // host numeric phase only (the device phase keeps its own, DLdl): the pivot shifts E_k in
+    // pivot order (empty: none, pivot_min = 0) and the report
+    std::vector<double> E;
+    FactorReport rep;
 };
 // Symbolic data of the up-looking factorization, for its numeric phase on the device
 // (ldl.hip): row patterns of L (ascending), each row entry's CSC slot, the Kp entries that seed
@@ -131,8 +152,13 @@ struct LdlSymbolic {
 // processed in ascending column order, so the device numeric phase (ldl.hip), which walks the
 // same pattern in the same order, reproduces L and D bit for bit.  numeric = false: structure
 // only (Lx, D left empty); sym: also return the symbolic data of the device phase.
+// Static pivot perturbation (engine option pivot_min = delta > 0; n = size of the (1,1) block):
+// with s_k = +1 where perm[k] < n and -1 otherwise -- the pivot signs of a symmetric
+// quasi-definite Kp under any symmetric ordering -- a pivot d with s_k * d < delta becomes
+// d' = s_k * delta, E_k = d' - d is recorded and later rows divide by d': the exact-arithmetic
+// factor of Kp + P*diag(E)*P'.  A NaN pivot throws as with delta = 0, where a zero pivot does too.
 Factor ldl_factor(const HCsr &Kp, const std::vector<int32_t> &perm, int nthreads, LdlSymbolic *sym = nullptr,
-                  bool numeric = true);
+                  bool numeric = true, double pivot_min = 0, int64_t n = -1);
 
 // ---- SpTRSV schedule ---------------------------------------------------------------------
 // The elimination tree is cut into blocks: sets of whole subtrees of at most R rows and at

@@ -109,6 +109,12 @@ void set_engine_option(EngineOpts &o, const std::string &name, const std::string
         if (end == value.c_str() || *end != '\0' || !std::isfinite(v) || !(v > 0 && v < 1))
             throw Error(CPK_ERR_ARGS, "engine option split_tol must be a number in (0, 1), got '" + value + "'");
         o.split_tol = v;
+    } else if (name == "pivot_min") {
+        char *end = nullptr;
+        const double v = strtod(value.c_str(), &end);
+        if (end == value.c_str() || *end != '\0' || !std::isfinite(v) || !(v >= 0))
+            throw Error(CPK_ERR_ARGS, "engine option pivot_min must be a finite number >= 0, got '" + value + "'");
+        o.pivot_min = v;
     } else if (name == "batch" || name == "r0_xcd_chunk") {
         char *end = nullptr;
         const long v = strtol(value.c_str(), &end, 10);
@@ -145,6 +151,11 @@ std::string get_engine_option(const EngineOpts &o, const std::string &name, bool
         snprintf(b, sizeof b, "%.17g", o.split_tol);
         return b;
     }
+    if (name == "pivot_min") {
+        char b[64];
+        snprintf(b, sizeof b, "%.17g", o.pivot_min);
+        return b;
+    }
     if (name == "batch") return std::to_string(o.batch);
     if (name == "r0_xcd_chunk") return std::to_string(o.r0_xcd_chunk);
     if (name == "chain_wide") return std::to_string(o.chain_wide);
@@ -162,6 +173,7 @@ EngineOpts engine_opts_from_env() {
     for (const BoolOpt &b : kBool) from(b.name);
     from("sweep");
     from("split_tol");
+    from("pivot_min");
     from("batch");
     from("r0_xcd_chunk");
     from("chain_wide");
@@ -176,6 +188,7 @@ std::string engine_opts_string(const EngineOpts &o, bool dist) {
     put("sweep");
     put("sweep_set");
     put("split_tol");
+    put("pivot_min");
     put("batch");
     put("r0_xcd_chunk");
     put("chain_wide");
@@ -211,6 +224,7 @@ uint64_t engine_opts_hash(const EngineOpts &o) {
     mix(sweep_str(o.sweep));
     mix(o.sweep_set ? "1" : "0");
     mix(get_engine_option(o, "split_tol"));
+    mix(get_engine_option(o, "pivot_min"));
     mix(std::to_string(o.batch));
     mix(std::to_string(o.r0_xcd_chunk));
     mix(std::to_string(o.chain_wide));

@@ -49,7 +49,7 @@ Analysis analyze(const HCsr &A11, const HCsr &B, const HCsr &C22, const EngineOp
     std::vector<int32_t> perm = order_kp(an.Kp, an.n, &an.ordering);
     pc.lap("order");
     an.device_numeric = device_numeric;
-    Factor f0 = ldl_factor(an.Kp, perm, 1, device_numeric ? &an.sym : nullptr, !device_numeric);
+    Factor f0 = ldl_factor(an.Kp, perm, 1, device_numeric ? &an.sym : nullptr, !device_numeric, o.pivot_min, an.n);
     pc.lap(device_numeric ? "factor (symbolic)" : "factor");
     // the hook reads Kp, f0 and an.sym on its own thread while this one only reads f0 too
     std::exception_ptr hook_err;
@@ -154,7 +154,7 @@ Precond *precond_create(Ctx &c, Analysis &&an, PrecondPre *pre) {
                 for (int64_t q = lo; q < hi; q++) bsrc[q] = an.rsrc[bsrc[q]];
             });
             if (pre && pre->dl.sym_ready) pc->dl = std::move(pre->dl);  // uploaded during the analysis
-            else dldl_setup_sym(pc->dl, an.sym, an.F0);
+            else dldl_setup_sym(pc->dl, an.sym, an.F0, an.n);
             dldl_setup_src(pc->dl, fsrc, bsrc, pc->S.order);
         } else {
             make_dfactor(an.F, pc->S, pc->dF, &key);
@@ -496,9 +496,9 @@ Precond *precond_create_dist(Ctx &c, Analysis &&an, const HCsr *Akry) {
         add(T.tsw.fval, 0), add(T.tsw.bval, 0), add(T.tsw.D, 1);
         add(pc->dKp.val, 2);
         add(pc->dKpl.val, 2), add(pc->tkr_val, 2), add(pc->dKpsl.val, 2);
-        dldl_setup(pc->dl, an.sym, an.F0, {}, {}, {});
+        dldl_setup(pc->dl, an.sym, an.F0, an.n, {}, {}, {});
         pc->kpg.upload(an.Kp.val);
-        dldl_numeric(c, pc->dl, pc->kpg.p, pc->dl.Lx.p, pc->dl.D.p);
+        dldl_numeric_own(c, pc->dl, pc->kpg.p);
         pc->fill_vmaps();
         CPK_HIP(hipStreamSynchronize(c.stream));
         an.F0.Lx.clear(), an.F0.D.clear();  // the exported values come from the device (dl)
@@ -574,6 +574,7 @@ struct AnalysisBcast {
         an.device_numeric = dn != 0;
         pod(an.Kp.nrows), pod(an.Kp.ncols), vec(an.Kp.ptr), vec(an.Kp.ind), vec(an.Kp.val);
         pod(an.F0.N), vec(an.F0.perm), vec(an.F0.Lp), vec(an.F0.Li), vec(an.F0.Lx), vec(an.F0.D), vec(an.F0.parent);
+        vec(an.F0.E), pod(an.F0.rep);
         LdlSymbolic &y = an.sym;
         pod(y.N), vec(y.Rp), vec(y.Rc), vec(y.Rcsc), vec(y.kp_ptr), vec(y.kp_tgt), vec(y.kp_src), vec(y.lev_ptr),
             vec(y.lev_rows);
@@ -696,7 +697,7 @@ Precond *precond_create(Ctx &c, const HCsr &A11, const HCsr &B, const HCsr &C22)
     if (dev)
         hook = [&](const HCsr &Kp, const Factor &f, const LdlSymbolic &sym) {
             CPK_HIP(hipSetDevice(c.device));
-            dldl_setup_sym(pre.dl, sym, f);
+            dldl_setup_sym(pre.dl, sym, f, A11.nrows);
             make_dmat(Kp, pre.dKp);
             pre.kp = true;
         };
@@ -723,12 +724,15 @@ double precond_refactor(Precond &p, const DMat &A11, const DMat &B, const DMat &
     if (p.dist) {
         // every rank refactors the whole system (as at construction) into scratch, then commits
         // its maps' values; collective-free, so each rank's result is the single-GPU one
-        DBuf<double> kpv, Lx, D;
+        DBuf<double> kpv, Lx, D, E;
+        FactorReport rep;
         kpv.alloc(std::max<size_t>(p.kpg.n, 1));
         Lx.alloc(p.dl.Lx.n);
         D.alloc(p.dl.D.n);
+        if (c.opts.pivot_min > 0) E.alloc(p.dl.D.n);
         dldl_assemble_kp(c, p.dl, A11.val.p, B.val.p, C22.val.p, kpv.p);
-        dldl_numeric(c, p.dl, kpv.p, Lx.p, D.p);
+        dldl_numeric(c, p.dl, kpv.p, Lx.p, D.p, E.p, rep);
+        dldl_commit_report(c, p.dl, E.p, rep);
         if (p.kpg.n) CPK_HIP(hipMemcpyAsync(p.kpg.p, kpv.p, p.kpg.bytes(), hipMemcpyDeviceToDevice, c.stream));
         CPK_HIP(hipMemcpyAsync(p.dl.Lx.p, Lx.p, Lx.bytes(), hipMemcpyDeviceToDevice, c.stream));
         CPK_HIP(hipMemcpyAsync(p.dl.D.p, D.p, D.bytes(), hipMemcpyDeviceToDevice, c.stream));
@@ -747,13 +751,17 @@ double precond_refactor(Precond &p, const DMat &A11, const DMat &B, const DMat &
         return s;
     }
     // all or nothing: the new Kp and factor are formed in scratch buffers; a bad pivot throws
-    // before anything the preconditioner holds (Kp, Kps, L, D, the sweep values) is touched
-    DBuf<double> kpv, Lx, D;
+    // before anything the preconditioner holds (Kp, Kps, L, D, the pivot shifts E, the factor
+    // report, the sweep values) is touched
+    DBuf<double> kpv, Lx, D, E;
+    FactorReport rep;
     kpv.alloc((size_t)std::max<int64_t>(p.dKp.nnz, 1));
     Lx.alloc(p.dl.Lx.n);
     D.alloc(p.dl.D.n);
+    if (c.opts.pivot_min > 0) E.alloc(p.dl.D.n);
     dldl_assemble_kp(c, p.dl, A11.val.p, B.val.p, C22.val.p, kpv.p);
-    dldl_numeric(c, p.dl, kpv.p, Lx.p, D.p);
+    dldl_numeric(c, p.dl, kpv.p, Lx.p, D.p, E.p, rep);
+    dldl_commit_report(c, p.dl, E.p, rep);
     // commit (copies, not buffer swaps: captured solver graphs hold these addresses)
     if (p.dKp.nnz) CPK_HIP(hipMemcpyAsync(p.dKp.val.p, kpv.p, p.dKp.val.bytes(), hipMemcpyDeviceToDevice, c.stream));
     CPK_HIP(hipMemcpyAsync(p.dl.Lx.p, Lx.p, Lx.bytes(), hipMemcpyDeviceToDevice, c.stream));

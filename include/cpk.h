@@ -34,7 +34,9 @@ typedef enum {
     CPK_ERR_ARGS = 3,       /* bad argument (reg_cpkrylov.m:122-125 "not enough inputs") */
     CPK_ERR_HIP = 4,        /* HIP runtime failure */
     CPK_ERR_RCCL = 5,       /* RCCL failure */
-    CPK_ERR_FACTOR = 6,     /* zero pivot in the static-pivot LDL' (ldl at opLDL2.m:82) */
+    CPK_ERR_FACTOR = 6,     /* the static-pivot LDL' (ldl at opLDL2.m:82) met a NaN pivot or, with the
+                               engine option pivot_min = 0 (the default), a zero one; a finished
+                               factor's signs are in cpk_pc_factor_report, never an error */
     CPK_ERR_NOMEM = 7,
     CPK_ERR_UNSUPPORTED = 8
 } cpk_status;
@@ -134,7 +136,11 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * must build identically).  A context starts from the CPK_<NAME> environment variables, read
  * once at creation; a change applies to preconditioners and solves created afterwards.
  * Names: sweep ("rows,cap,threads[,rows,cap,threads[,sub0]]"; unset, each path has its own
- * default: a distributed context reports and uses the distributed one), split_tol, host_factor,
+ * default: a distributed context reports and uses the distributed one), split_tol, pivot_min
+ * (delta, a finite number >= 0, default 0 = off: a pivot of the LDL' whose expected sign s gives
+ * s * d < delta is replaced by s * delta, see cpk_pc_factor_report; the one option besides
+ * exact_dots that changes results; read at every cpk_pc_create[_hint], cpk_pc_refactor and
+ * cpk_analyze), host_factor,
  * no_pipe, no_upper, no_col16, no_dataflow, all_dataflow, no_colsweep, all_colsweep, no_chain, chain_wide
  * (rounds of at most this many blocks join the sweep chain, default 256), exact_dots, no_bcast_analysis
  * (every rank of a distributed preconditioner runs the global analysis instead of receiving rank 0's),
@@ -212,7 +218,8 @@ int cpk_pc_destroy(cpk_pc M);
  * through reg_cpkrylov.m:131).  Kp and the numeric LDL' (opLDL2.m:81-82) are recomputed on
  * the device from the matrices' device copies; ordering, elimination tree and sweep schedule
  * are reused.  The factors equal those of a fresh cpk_pc_create on the same values, bit for
- * bit.  Single GPU; CPK_ERR_ARGS when the sparsity differs, CPK_ERR_FACTOR on a zero pivot.
+ * bit.  CPK_ERR_ARGS when the sparsity differs, CPK_ERR_FACTOR on a bad pivot (the previous
+ * factors, pivot shifts and report then stay).
  * ptime: seconds of the refactorization. */
 int cpk_pc_refactor(cpk_pc M, cpk_mat A11, cpk_mat B, cpk_mat C22, double *ptime);
 /* M.nitref = ...; M.itref_tol = ...; etc. (opLDL2.m:45-50, 97-115), has_* fields select. */
@@ -297,6 +304,31 @@ int cpk_pc_local_dofs(cpk_pc M, int64_t *n_loc, int64_t *m_loc, int32_t *dofs);
 /* Export the factors P'*Kp*P = L*D*L': strict-lower L in CSC (Lcolptr[N+1], Lrowind[nnz_l],
  * Lval[nnz_l]), D[N], perm[N] (perm[k] = original index of pivot k).  Any pointer may be NULL. */
 int cpk_pc_export(cpk_pc M, int64_t *Lcolptr, int32_t *Lrowind, double *Lval, double *D, int32_t *perm);
+/* What the last successful factorization (create or refactor) found.  Stands in for the inertia
+ * and pivot information MA57's ldl returns with the factors at opLDL2.m:81-82.  Positions are
+ * pivot positions: the index into the exported D and perm, the numbering of CPK_ERR_FACTOR's
+ * message.  s_k = +1 where perm[k] < n (a dof of the (1,1) block), -1 otherwise: the pivot signs
+ * of a symmetric quasi-definite Kp under any symmetric ordering.
+ * Engine option pivot_min = delta > 0: a pivot d with s_k * d < delta is replaced by
+ * d' = s_k * delta and E_k = d' - d recorded, so the factors are those of Kp + P*diag(E)*P'
+ * exactly; Kp itself (the refinement residual, divide, the solvers) stays the unperturbed matrix,
+ * and iterative refinement (nitref, force_itref) corrects towards it.  A refactorization that
+ * fails leaves the previous factors, shifts and report in place. */
+typedef struct {
+    int64_t n_pos, n_neg;      /* signs of D = inertia of the factored matrix (Sylvester) */
+    int64_t n_wrong;           /* pivots with s_k * d < 0 */
+    int64_t first_wrong;       /* lowest such pivot position, -1 if none */
+    int64_t n_perturbed;       /* pivots replaced under pivot_min */
+    int64_t argmin_abs;        /* position of min |d|, lowest on ties; -1 if N == 0 */
+    double  min_abs, max_abs;  /* over D */
+    double  max_shift;         /* max |E_k| */
+    double  pivot_min;         /* the value in effect at this factorization */
+} cpk_factor_report;
+int cpk_pc_factor_report(cpk_pc M, cpk_factor_report *out);
+/* The pivot shifts of that factorization (the perturbation MA57's pivoting makes unnecessary at
+ * opLDL2.m:81-82): N values in the ORIGINAL dof order, E[perm[k]] = E_k; zeros when none.  On a
+ * distributed preconditioner N is the global size and every rank holds the same values. */
+int cpk_pc_pivot_shift(cpk_pc M, double *E);
 
 /* ---- host-only analysis (no GPU needed) ------------------------------------------------- */
 /* The host half of cpk_pc_create: Kp assembly, fill-reducing ordering, static-pivot LDL' and
@@ -310,6 +342,10 @@ int cpk_analysis_destroy(cpk_analysis an);
 int cpk_analysis_get_info(cpk_analysis an, cpk_pc_info *info);
 int cpk_analysis_export(cpk_analysis an, int64_t *Lcolptr, int32_t *Lrowind, double *Lval, double *D,
                         int32_t *perm);
+/* cpk_pc_factor_report / cpk_pc_pivot_shift of the host numeric phase (the inertia and pivot
+ * information of MA57's ldl, opLDL2.m:81-82): equal to the device's, bit for bit. */
+int cpk_analysis_factor_report(cpk_analysis an, cpk_factor_report *out);
+int cpk_analysis_pivot_shift(cpk_analysis an, double *E);
 /* Sweep schedule: round_ptr[nrounds+1] (blocks per round), blk_lvl[nblocks+1] (levels per
  * block, indices into lvl_row), lvl_row[nlevels+1] (first position of each level; last = N),
  * order[N] (order[q] = exported-factor row solved at schedule position q).  Each row sums its

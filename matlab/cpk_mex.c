@@ -191,7 +191,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     mxGetString(prhs[0], cmd, sizeof cmd);
     {   /* argument counts before anything is converted or a device is touched */
         static const struct { const char *cmd; int nrhs; } need[] = {
-            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_apply_multi", 3}, {"pc_divide", 3}, {"pc_destroy", 2},
+            {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_apply_multi", 3}, {"pc_divide", 3}, {"pc_destroy", 2}, {"pc_factor_report", 2},
             {"method", 6}, {"reg_solve", 7}, {"method_solve_multi", 6}};
         int i;
         for (i = 0; i < (int)(sizeof need / sizeof need[0]); i++)
@@ -240,6 +240,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         st = cmd[3] == 'a' ? cpk_pc_apply(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]))
                            : cpk_pc_divide(M, mxGetPr(ARG(2)), mxGetPr(plhs[0]));
         if (st) fail(st);
+    } else if (!strcmp(cmd, "pc_factor_report")) {
+        /* [report, E] = cpk_mex('pc_factor_report', M): the inertia and pivot information MA57's
+         * ldl returns with the factors (opLDL2.m:81-82); positions are 0-based pivot positions */
+        static const char *rf[] = {"n_pos", "n_neg", "n_wrong", "first_wrong", "n_perturbed", "argmin_abs",
+                                   "min_abs", "max_abs", "max_shift", "pivot_min"};
+        cpk_pc M = to_pc(ARG(1));
+        cpk_factor_report r;
+        if ((st = cpk_pc_factor_report(M, &r))) fail(st);
+        plhs[0] = mxCreateStructMatrix(1, 1, 10, rf);
+        mxSetField(plhs[0], 0, "n_pos", mxCreateDoubleScalar((double)r.n_pos));
+        mxSetField(plhs[0], 0, "n_neg", mxCreateDoubleScalar((double)r.n_neg));
+        mxSetField(plhs[0], 0, "n_wrong", mxCreateDoubleScalar((double)r.n_wrong));
+        mxSetField(plhs[0], 0, "first_wrong", mxCreateDoubleScalar((double)r.first_wrong));
+        mxSetField(plhs[0], 0, "n_perturbed", mxCreateDoubleScalar((double)r.n_perturbed));
+        mxSetField(plhs[0], 0, "argmin_abs", mxCreateDoubleScalar((double)r.argmin_abs));
+        mxSetField(plhs[0], 0, "min_abs", mxCreateDoubleScalar(r.min_abs));
+        mxSetField(plhs[0], 0, "max_abs", mxCreateDoubleScalar(r.max_abs));
+        mxSetField(plhs[0], 0, "max_shift", mxCreateDoubleScalar(r.max_shift));
+        mxSetField(plhs[0], 0, "pivot_min", mxCreateDoubleScalar(r.pivot_min));
+        if (nlhs > 1) {
+            cpk_pc_info info;
+            if ((st = cpk_pc_get_info(M, &info))) fail(st);
+            plhs[1] = mxCreateDoubleMatrix((mwSize)info.N, 1, mxREAL);
+            if (info.N > 0 && (st = cpk_pc_pivot_shift(M, mxGetPr(plhs[1])))) fail(st);
+        }
     } else if (!strcmp(cmd, "pc_destroy")) {
         cpk_pc_destroy(to_pc(ARG(1)));
     } else if (!strcmp(cmd, "method")) {

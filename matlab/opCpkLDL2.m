@@ -69,6 +69,14 @@ classdef opCpkLDL2 < opSpot
       function opOut = ctranspose(op)
          opOut = opCpkLDLFactor(op.h, op.nA + op.nC);
       end
+      % What the factorization found: the inertia and pivot information MA57's ldl returns
+      % with the factors (opLDL2.m:81-82).  rep: struct with n_pos, n_neg (the inertia),
+      % n_wrong, first_wrong, n_perturbed, argmin_abs, min_abs, max_abs, max_shift, pivot_min
+      % (positions are 0-based pivot positions); E: the pivot shifts in the original dof order
+      % (the factors are those of Kp + diag(E); zeros unless CPK_PIVOT_MIN replaced pivots)
+      function [rep, E] = factor_report(op)
+         [rep, E] = cpk_mex('pc_factor_report', op.h.id);
+      end
       % double (opLDL2.m:138-149): the dense matrix, one column op * e_i at a time -- the same
       % products the reference forms (each a device apply with the current properties)
       function x = double(op)
