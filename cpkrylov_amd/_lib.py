@@ -41,6 +41,11 @@ class FactorReport(C.Structure):
                [(k, C.c_double) for k in ("min_abs", "max_abs", "max_shift", "pivot_min")]
 
 
+class RowspanInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("eligible", "r0", "nr", "ne", "slots", "ndr", "nrp", "trips")] + \
+               [("dset", C.c_uint64 * 2)]
+
+
 class PcInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n", "m", "N", "nnz_kp", "nnz_l", "nblocks", "nrounds",
                                          "max_block_levels", "depth", "ordering")]
@@ -103,6 +108,9 @@ _SIGS = {
                             C.c_int),
     "cpk_analysis_schedule": ([vp, P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int32)], C.c_int),
     "cpk_analysis_plan": ([vp, vp, vp, C.c_int, C.c_int, P(vp)], C.c_int),
+    "cpk_analysis_rowspan": ([vp, C.c_int64, C.c_int, C.c_int64, P(RowspanInfo), P(C.c_int64), P(C.c_int32),
+                              P(C.c_double), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_uint64), P(C.c_int32),
+                              P(C.c_int32), P(C.c_int32), P(C.c_uint8)], C.c_int),
     "cpk_plan_array": ([vp, C.c_char_p, P(C.c_int64), vp], C.c_int),
     "cpk_plan_destroy": ([vp], C.c_int),
     "cpk_simgroup_create": ([C.c_int, P(vp)], C.c_int),

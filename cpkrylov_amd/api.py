@@ -431,6 +431,17 @@ class opLDL2:
         return dict(zip(("rounds", "round0_blocks", "upper_blocks", "round0_assigned", "resid_assigned",
                          "bwd_assigned", "persistent", "chain_tasks"), list(v)))
 
+    def block_model(self):
+        """Diagnostic: the upper rounds' loop-cost model (cpk_debug_block_model), one row per
+        (upper block, direction): block, direction (0 forward), rows, level trips, dataflow trips,
+        outside terms behind in-block ones, column sweep valid, loop chosen (0 level, 1 dataflow,
+        2 / 3 column sweep without / with drains, 4 row-span), row-span eligible, its drain trips."""
+        n = C.c_int64(0)
+        check(lib.cpk_debug_block_model(self.h, None, 1 << 40, C.byref(n)))
+        mod = np.zeros(max(n.value, 1), np.int64)
+        check(lib.cpk_debug_block_model(self.h, mod.ctypes.data_as(_P(C.c_int64)), n.value, C.byref(n)))
+        return mod[:n.value].reshape(-1, 10)
+
     def local_dofs(self):
         """Global indices of this rank's local vector entries ([x-part; y-part]) and n_loc."""
         nl, ml = C.c_int64(), C.c_int64()
@@ -584,6 +595,47 @@ _PLAN_NAMES = ("sizes", "dofs", "node_rank", "T", "fsub_Lp", "fsub_Li", "fsub_Lx
                "fsub_parent", "fsub_key", "extra_ptr", "extra_col", "extra_key", "extra_val", "tf_ptr", "tf_col",
                "tf_val", "tf_src", "tb_ptr", "tb_col", "tb_val", "DT", "tlev_ptr", "tlev_rows", "tsend", "tdof") + \
     tuple(f"{k}_{a}" for k in ("kp", "ac", "ab") for a in ("ptr", "col", "val", "send"))
+
+
+def rowspan_layouts(A, B, Cm, ctx=None, options=None, cap_entries=0):
+    """Host-only (no GPU): the row-span layout (cpk_analysis_rowspan) of every upper-round block of
+    opLDL2(A, B, C)'s sweep schedule and both directions, as the device layout builds it.  A list
+    of dicts: block, dir, eligible, r0, nr, rowptr, col, val, step and, where eligible, slots, ndr,
+    nrp, trips, dset, dest, lead, mask (nr x 2, by step), base, first, run0 (by step), tab
+    (ndr x nrp)."""
+    mats = [M if isinstance(M, Matrix) else Matrix(M, host_only=True) for M in (A, B, Cm)]
+    h = C.c_void_p()
+    check(lib.cpk_analyze(mats[0].h, mats[1].h, mats[2].h, _options_spec(ctx, options), C.byref(h)))
+    out = []
+    try:
+        info = _lib.PcInfo()
+        check(lib.cpk_analysis_get_info(h, C.byref(info)))
+        rp = np.empty(info.nrounds + 1, np.int64)
+        check(lib.cpk_analysis_schedule(h, None, rp.ctypes.data_as(_P(C.c_int64)), None, None, None))
+        i32, i64 = (lambda n: np.zeros(max(n, 1), np.int32)), (lambda n: np.zeros(max(n, 1), np.int64))
+        ptr = lambda a, t: a.ctypes.data_as(_P(t))  # noqa: E731
+        for b in range(int(rp[1]) if len(rp) > 2 else int(rp[-1]), int(rp[-1])):
+            for d in (0, 1):
+                ri = _lib.RowspanInfo()
+                check(lib.cpk_analysis_rowspan(h, b, d, cap_entries, C.byref(ri), *([None] * 11)))
+                nr, ne = ri.nr, ri.ne
+                rowptr, col, val, dest, step, lead = i64(nr + 1), i32(ne), np.zeros(max(ne, 1)), i32(ne), i32(nr), i32(nr)
+                mask, base, first, run0 = np.zeros(2 * max(nr, 1), np.uint64), i32(nr), i32(nr), i32(nr)
+                tab = np.zeros(max(ri.ndr * ri.nrp, 1), np.uint8)
+                check(lib.cpk_analysis_rowspan(h, b, d, cap_entries, C.byref(ri), ptr(rowptr, C.c_int64), ptr(col, C.c_int32),
+                                               _dptr(val), ptr(dest, C.c_int32), ptr(step, C.c_int32),
+                                               ptr(lead, C.c_int32), ptr(mask, C.c_uint64), ptr(base, C.c_int32),
+                                               ptr(first, C.c_int32), ptr(run0, C.c_int32), ptr(tab, C.c_uint8)))
+                r = dict(block=b, dir=d, eligible=bool(ri.eligible), r0=ri.r0, nr=nr, rowptr=rowptr[:nr + 1],
+                         col=col[:ne], val=val[:ne], step=step[:nr])
+                if ri.eligible:
+                    r.update(slots=ri.slots, ndr=ri.ndr, nrp=ri.nrp, trips=ri.trips, dset=(int(ri.dset[0]), int(ri.dset[1])),
+                             dest=dest[:ne], lead=lead[:nr], mask=mask[:2 * nr].reshape(nr, 2), base=base[:nr],
+                             first=first[:nr], run0=run0[:nr], tab=tab[:ri.ndr * ri.nrp].reshape(ri.ndr, ri.nrp))
+                out.append(r)
+    finally:
+        lib.cpk_analysis_destroy(h)
+    return out
 
 
 def dist_plan(G, B, Cneg, A, Cop, nranks, rank, ctx=None, options=None):

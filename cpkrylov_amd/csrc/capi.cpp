@@ -148,6 +148,9 @@ struct cpk_mat_s {
 struct cpk_analysis_s {
     Analysis an;
     EngineOpts opts;  // the options it was built with (cpk_analysis_plan's split_tol)
+    // cpk_analysis_rowspan's last export (a caller asks twice: the sizes, then the arrays)
+    RsExport rs_last;
+    int64_t rs_key[3] = {-1, -1, -1};
 };
 
 struct cpk_plan_s {
@@ -1049,7 +1052,14 @@ int cpk_debug_pass_times(cpk_ctx ctx, double *out) {
 int cpk_debug_block_model(cpk_pc M, int64_t *out, int64_t n, int64_t *copied) {
     API_BEGIN
     need(M && copied, "NULL argument");
-    const std::vector<int64_t> &h = M->p->dF.hmodel;
+    // the rank's own sweeps, then (a distributed separator solved by the block sweeps) the T
+    // sweep's, its directions reported as 2 (forward) and 3 (backward)
+    std::vector<int64_t> h = M->p->dF.hmodel;
+    if (M->p->sep.tsweep) {
+        const size_t at = h.size();
+        h.insert(h.end(), M->p->sep.tsw.hmodel.begin(), M->p->sep.tsw.hmodel.end());
+        for (size_t i = at + 1; i < h.size(); i += kBlockModelW) h[i] += 2;
+    }
     *copied = std::min<int64_t>(n, (int64_t)h.size());
     if (out && *copied) std::memcpy(out, h.data(), (size_t)*copied * sizeof(int64_t));
     API_END
@@ -1200,6 +1210,35 @@ int cpk_analysis_schedule(cpk_analysis a, int64_t *nlevels, int64_t *round_ptr, 
     if (round_ptr) std::memcpy(round_ptr, s.round_ptr.data(), s.round_ptr.size() * sizeof(int64_t));
     if (blk_lvl) std::memcpy(blk_lvl, s.blk_lvl.data(), s.blk_lvl.size() * sizeof(int64_t));
     if (lvl_row) std::memcpy(lvl_row, s.lvl_row.data(), s.lvl_row.size() * sizeof(int64_t));
+    API_END
+}
+
+int cpk_analysis_rowspan(cpk_analysis a, int64_t block, int dir, int64_t cap_entries, cpk_rowspan_info *info,
+                         int64_t *rowptr, int32_t *col, double *val, int32_t *dest, int32_t *step, int32_t *lead,
+                         uint64_t *mask, int32_t *base, int32_t *first, int32_t *run0, uint8_t *tab) {
+    API_BEGIN
+    need(a && info, "NULL argument");
+    if (a->rs_key[0] != block || a->rs_key[1] != dir || a->rs_key[2] != cap_entries) {
+        a->rs_key[0] = -1;
+        rowspan_export(a->an.F, a->an.S, block, dir, cap_entries, a->an.sweep.cap[1], a->rs_last);
+        a->rs_key[0] = block, a->rs_key[1] = dir, a->rs_key[2] = cap_entries;
+    }
+    const RsExport &x = a->rs_last;
+    info->eligible = x.eligible ? 1 : 0, info->r0 = x.r0, info->nr = x.nr, info->ne = x.ne, info->slots = x.slots;
+    info->ndr = x.ndr, info->nrp = x.nrp, info->trips = x.trips, info->dset[0] = x.dset[0], info->dset[1] = x.dset[1];
+    auto put = [](auto *dst, const auto &v) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof v[0]);
+    };
+    put(rowptr, x.rowptr), put(col, x.col), put(val, x.val), put(step, x.step);
+    if (x.eligible) {
+        put(dest, x.dest), put(lead, x.lead), put(tab, x.tab);
+        for (size_t t = 0; t < x.rows.size(); t++) {
+            if (mask) mask[2 * t] = x.rows[t].mlo, mask[2 * t + 1] = x.rows[t].mhi;
+            if (base) base[t] = x.rows[t].base;
+            if (first) first[t] = x.rows[t].first;
+            if (run0) run0[t] = x.rows[t].run0;
+        }
+    }
     API_END
 }
 

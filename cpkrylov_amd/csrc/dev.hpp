@@ -120,6 +120,9 @@ struct EngineOpts {
     bool all_dataflow = false;    // all_dataflow:       upper rounds always on the dataflow loop (tests)
     bool no_colsweep = false;     // no_colsweep:        upper rounds never on the column sweep
     bool all_colsweep = false;    // all_colsweep:       upper blocks of <= 256 rows always on the column sweep (tests)
+    bool no_rowspan = false;      // no_rowspan:         upper rounds never on the row-span loop
+    bool all_rowspan = false;     // all_rowspan:        every eligible upper block on the row-span loop (tests; goes
+                                  //                     before all_dataflow / all_colsweep, which the model's pick does not)
     bool no_sched_resid = false;  // no_sched_resid:     refinement residual in original order
     bool no_fused_resid = false;  // no_fused_resid:     refinement residual as its own SpMV
     int r0_xcd_chunk = 16;        // r0_xcd_chunk:       K > 0: runs of K consecutive round-0 blocks share an XCD
@@ -262,6 +265,30 @@ struct MultiPlan {
     int64_t launches = 0, staged = 0, direct = 0;
 };
 
+// The row-span loop of an upper-round block (levels_rowspan, kernels.hip), per direction.  The
+// block's staged image is a slot array (8 bytes a slot, no column codes): the rows' leading outside
+// products, then each row's in-block values stored dense by step from the row's first in-block
+// step to its own ("span"), then each row's outside products behind in-block terms ("runs").
+// RsBlk: one per upper block; slots == 0: the block is not on the loop.
+struct RsBlk {
+    uint64_t dlo, dhi;  // the steps after which some row subtracts a run (the drain steps)
+    uint32_t tab;       // byte offset of the block's run lengths in DFactor::urtab: [drain step][step of the row]
+    uint16_t slots;     // slots of the image (guards included); the run lengths are staged behind them
+    uint16_t ndr;       // drain steps
+    uint32_t nrp, pad;  // row stride of the run lengths (64 or 128)
+};
+// RsRow: one per row, stored by the row's step in its block ([first row of the block - urow0 + step])
+struct RsRow {
+    uint64_t mlo, mhi;  // bit t: the row has an in-block term at step t
+    int32_t base;       // slot of the row's first in-block step; step t is slot base + (t - first)
+    int32_t first;      // the row's first in-block step (its own step if it has none)
+    int32_t run0;       // slot of the row's first run term
+    int32_t pad;
+};
+// the layout's limits: rows of a block, run length (a byte of the table), staged table bytes
+constexpr int kRowspanMaxRows = 128, kRowspanMaxRun = 255, kRowspanMaxTab = 2048;
+constexpr int kRowspanGuard = 4, kRowspanEndGuard = 8;  // slots before the leads / behind the spans; behind the runs
+
 // HBM-resident factor + sweep schedule (rows in schedule order).
 struct DFactor {
     int64_t N = 0, nnz = 0, nblk = 0, nlvl = 0;
@@ -277,6 +304,17 @@ struct DFactor {
     // behind it << 8; outside, kCsOut.  ucode[dir][e - ucode0[dir]] for entry e of fcol / bcol
     DBuf<int16_t> ucode[2];
     uint32_t ucode0[2] = {0, 0};
+    // the row-span loop's layout (kernels.hip, mark_dataflow): for a block on it ucode holds each
+    // entry's destination slot instead; urlead the first lead slot of each row, laid out as ufold;
+    // urblk[dir][block - ublk0]; urrow[dir][row]; urtab[dir] the run-length tables.  hrs_cap: the
+    // entry capacity a launch image needs for block ublk0 + i (both directions; 0: not on the loop)
+    DBuf<int16_t> urlead;
+    DBuf<RsBlk> urblk[2];
+    DBuf<RsRow> urrow[2];
+    DBuf<uint8_t> urtab[2];
+    int64_t ublk0 = 0;
+    std::vector<int32_t> hrs_cap;
+    int rowspan = 0;        // the row-span loop (levels_rowspan): 0 the host model per block, 1 never, 2 every eligible block
     DBuf<int16_t> fcol16;  // round 0 when every forward entry is local: column - block's first row (else empty)
     int64_t nnz16 = 0;     // forward entries stored in fcol16 (10 bytes each instead of 12)
     DBuf<double> fval;
@@ -325,10 +363,32 @@ struct DFactor {
     std::vector<char> round_fits;    // host: every block of round r fits (sweep_rows[1], sweep_cap[1])
     int sweep_rows[2] = {192, 1024}, sweep_cap[2] = {576, 4096}, sweep_threads[2] = {64, 512};  // round 0 / rest
     size_t bytes() const {
-        return fptr.bytes() + fcol.bytes() + fcol16.bytes() + ufold.bytes() + ustep.bytes() + ucode[0].bytes() + ucode[1].bytes() + fval.bytes() + bptr.bytes() + bcol.bytes() + bval.bytes() + D.bytes() +
+        return fptr.bytes() + fcol.bytes() + fcol16.bytes() + ufold.bytes() + ustep.bytes() + ucode[0].bytes() + ucode[1].bytes() + urlead.bytes() + urblk[0].bytes() + urblk[1].bytes() + urrow[0].bytes() + urrow[1].bytes() + urtab[0].bytes() + urtab[1].bytes() + fval.bytes() + bptr.bytes() + bcol.bytes() + bval.bytes() + D.bytes() +
                perm.bytes() + blk_lvl.bytes() + lvl_row.bytes() + meta.bytes();
     }
 };
+// The row-span layout of one upper block and direction, built on the host alone from the
+// relabelled factor and its schedule (cpk_analysis_rowspan: the layout can be checked without a
+// GPU).  It restates make_dfactor's entry order (forward rows by ascending key, backward by
+// descending key; no BwdExtra entries: a single-GPU factor) instead of reading its arrays, and
+// scans the factor's columns per block: for test sizes.  The GPU tests tie the order to the device's.  Rows are the block's local rows; cap_entries: the
+// image's entry capacity (<= 0: the schedule's).  eligible = false: the block is refused.
+struct RsExport {
+    bool eligible = false;
+    int64_t r0 = 0, nr = 0, ne = 0, slots = 0, ndr = 0, nrp = 0, trips = 0;
+    uint64_t dset[2] = {0, 0};
+    std::vector<int64_t> rowptr;   // [nr + 1] into col / val / dest
+    std::vector<int32_t> col;      // relabelled rows; in-block: [r0, r0 + nr)
+    std::vector<double> val;
+    std::vector<int32_t> dest, step, lead;  // per entry; per local row; per local row
+    std::vector<RsRow> rows;       // by step
+    std::vector<uint8_t> tab;      // [ndr][nrp]
+};
+struct Factor;
+struct Schedule;
+void rowspan_export(const Factor &f, const Schedule &s, int64_t block, int dir, int64_t cap_entries, int sched_cap,
+                    RsExport &out);
+
 // a backward-sweep entry of row q referring to a row outside the factor (col >= N)
 struct BwdExtra {
     int32_t col;
@@ -583,7 +643,7 @@ constexpr int64_t kSepPiggy = 2;  // spare payload slots per rank in the separat
 // there with the next vector's halo (solvers.hip, cpminres)
 // block record flags (DFactor::meta, the l1 field): the dataflow level loop per direction for
 // an upper-round block (mark_dataflow, kernels.hip); every reader of l1 masks them off
-constexpr int kBlockModelW = 8;  // fields per (upper block, direction) of DFactor::hmodel
+constexpr int kBlockModelW = 10;  // fields per (upper block, direction) of DFactor::hmodel
 constexpr int32_t kMetaDfFwd = 1 << 30, kMetaDfBwd = 1 << 29, kMetaCsFwd = 1 << 28, kMetaCsBwd = 1 << 27,
                   kMetaCoFwd = 1 << 26, kMetaCoBwd = 1 << 25, kMetaL1Mask = (1 << 25) - 1;
 constexpr int64_t kKrylovSpare = 2;

@@ -132,6 +132,17 @@ constexpr double kColsweepStepDrainCycles[4] = {297.0, 353.0, 430.0, 500.0};
 constexpr int kCsOut = 0x8000, kCsStep = 0x80ff, kCsRunMax = 127;
 constexpr double kColsweepDrainCycles[4] = {261.0, 617.0, 800.0, 1000.0};  // a drain trip (four terms a row)
 constexpr double kLevelTripCycles = 290.0, kDataflowTripCycles[2] = {272.0, 190.0};
+// the row-span loop (levels_rowspan): cycles per step at 1 / 2 rows per lane and per drain trip
+// (up to four terms a row, or eight where a run is longer)
+// (fitted on the stamps build over every upper block of the +-64 window with the loop forced on
+// and off, profiles/r07_rowspan_calibration.txt)
+constexpr int64_t kRowspanNarrowRound = 256;  // rounds of at most this many blocks keep the kernel's image
+constexpr double kRowspanBaseCycles = 1000.0;
+// what a row-span block's staging costs over the other loops' (scattered stores, its record and
+// run-length table): 1.4-2.6 K cycles a block in the same stamps
+constexpr double kRowspanStagingCycles = 2000.0;
+constexpr double kRowspanStepCycles[2] = {140.0, 180.0};
+constexpr double kRowspanDrainCycles = 380.0;
 #ifndef CPK_UPPER_DATAFLOW
 #define CPK_UPPER_DATAFLOW 1
 #endif
@@ -214,7 +225,9 @@ int64_t dataflow_trips(const std::vector<std::vector<int>> &terms, bool bwd, int
 template <class Key>
 static std::vector<int16_t> build_ufold(DFactor &d, const std::vector<int32_t> &meta, const std::vector<int64_t> &round_ptr,
                         const std::vector<uint32_t> &fptr, const std::vector<int32_t> &fcol,
-                        const std::vector<uint32_t> &bptr, const std::vector<int32_t> &bcol, const Key &key) {
+                        const std::vector<uint32_t> &bptr, const std::vector<int32_t> &bcol, const Key &key,
+                        std::vector<int16_t> (&code)[2]) {
+    code[0].clear(), code[1].clear();
     d.ufold.release();
     d.ustep.release();
     d.ucode[0].release(), d.ucode[1].release();
@@ -225,8 +238,7 @@ static std::vector<int16_t> build_ufold(DFactor &d, const std::vector<int32_t> &
     for (int64_t b = ub0; b < ub1; b++) lo = std::min<int64_t>(lo, meta[(size_t)b * 8]), hi = std::max<int64_t>(hi, meta[(size_t)b * 8 + 1]);
     if (lo >= hi) return {};
     std::vector<int16_t> uf((size_t)(2 * (hi - lo)), 0), us((size_t)(2 * (hi - lo)), 0);
-    std::vector<int16_t> code[2] = {std::vector<int16_t>((size_t)(fptr[hi] - fptr[lo]), 0),
-                                    std::vector<int16_t>((size_t)(bptr[hi] - bptr[lo]), 0)};
+    code[0].assign((size_t)(fptr[hi] - fptr[lo]), 0), code[1].assign((size_t)(bptr[hi] - bptr[lo]), 0);
     parallel_for(ub1 - ub0, [&](int64_t a, int64_t z) {
         std::vector<std::pair<int64_t, int32_t>> order;
         for (int64_t b = ub0 + a; b < ub0 + z; b++) {
@@ -273,19 +285,214 @@ static std::vector<int16_t> build_ufold(DFactor &d, const std::vector<int32_t> &
     d.urow0 = (int32_t)lo;
     d.ufold.upload(uf);
     d.ustep.upload(us);
-    d.ucode[0].upload(code[0]), d.ucode[1].upload(code[1]);
     d.ucode0[0] = fptr[lo], d.ucode0[1] = bptr[lo];
     return us;
 }
+
+// The row-span layout of one block and direction (RsBlk / RsRow, dev.hpp).  step(k): the step of
+// local row k.  Returns false where the block is not eligible: more than kRowspanMaxRows rows, a
+// row whose in-block terms are not at increasing steps before its own (the column sweep's order
+// condition), a run longer than a byte, or an image over cap_bytes.  Slots, in order: a guard, the
+// rows' leading outside terms (by local row), the spans (by step), a guard, the runs (by step), a
+// guard; the guards keep the level loop's clamped group reads inside the image.
+struct RsLayout {
+    int nr = 0, slots = 0, ndr = 0, nrp = 0;
+    int64_t trips = 0;             // drain trips (the cost model)
+    size_t bytes = 0;              // slots and the staged run lengths
+    uint64_t dset[2] = {0, 0};
+    std::vector<int16_t> dest;     // per entry of the block, in entry order
+    std::vector<int16_t> lead;     // per local row: its first lead slot
+    std::vector<RsRow> rows;       // by step
+    std::vector<uint8_t> tab;      // [drain step][step of the row]
+};
+template <class Step>
+static bool rowspan_layout(int r0, int r1, const std::vector<uint32_t> &ptr, const std::vector<int32_t> &col,
+                           const Step &step, size_t cap_bytes, RsLayout &L) {
+    const int nr = r1 - r0;
+    if (nr < 1 || nr > kRowspanMaxRows) return false;
+    L = RsLayout{};
+    L.nr = nr, L.nrp = nr <= kWave ? kWave : 2 * kWave;
+    L.rows.assign((size_t)nr, RsRow{0, 0, 0, 0, 0, 0});
+    L.lead.assign((size_t)nr, 0);
+    L.dest.assign((size_t)(ptr[r1] - ptr[r0]), 0);
+    std::vector<int> nlead((size_t)nr, 0), nrun((size_t)nr, 0), rowof((size_t)nr, -1);
+    // per (drain step, row's step): the run behind the row's in-block term of that step
+    std::vector<std::array<int, 3>> runs;  // (step of the in-block term, row's step, length)
+    for (int k = 0; k < nr; k++) {
+        const int s = step(k);
+        if (s < 0 || s >= nr || rowof[(size_t)s] >= 0) return false;
+        rowof[(size_t)s] = k;
+        RsRow &R = L.rows[(size_t)s];
+        R.first = s;
+        int prev = -1, run = 0;
+        for (uint32_t e = ptr[r0 + k]; e < ptr[r0 + k + 1]; e++) {
+            const int32_t c = col[e];
+            if (c >= r0 && c < r1) {
+                const int t = step(c - r0);
+                if (t <= prev || t >= s) return false;
+                if (prev >= 0 && run) runs.push_back({prev, s, run});
+                if (prev < 0) R.first = t;
+                (t < 64 ? R.mlo : R.mhi) |= 1ull << (t & 63);
+                prev = t, run = 0;
+            } else if (prev < 0) {
+                nlead[(size_t)k]++;
+            } else {
+                run++, nrun[(size_t)k]++;
+            }
+        }
+        if (prev >= 0 && run) runs.push_back({prev, s, run});
+    }
+    int at = kRowspanGuard;
+    for (int k = 0; k < nr; k++) L.lead[(size_t)k] = (int16_t)std::min(at, (int)INT16_MAX), at += nlead[(size_t)k];
+    for (int s = 0; s < nr; s++) L.rows[(size_t)s].base = at, at += s - L.rows[(size_t)s].first;
+    at += kRowspanGuard;
+    for (int s = 0; s < nr; s++) L.rows[(size_t)s].run0 = at, at += nrun[(size_t)rowof[(size_t)s]];
+    at += kRowspanEndGuard;
+    if (at > INT16_MAX) return false;
+    L.slots = at;
+    for (const auto &r : runs) {
+        if (r[2] > kRowspanMaxRun) return false;
+        L.dset[r[0] >> 6] |= 1ull << (r[0] & 63);
+    }
+    L.ndr = __builtin_popcountll(L.dset[0]) + __builtin_popcountll(L.dset[1]);
+    L.tab.assign((size_t)L.ndr * (size_t)L.nrp, 0);
+    auto drain_index = [&](int t) {
+        return t < 64 ? __builtin_popcountll(L.dset[0] & ((1ull << t) - 1))
+                      : __builtin_popcountll(L.dset[0]) + __builtin_popcountll(L.dset[1] & ((1ull << (t - 64)) - 1));
+    };
+    std::vector<int> kmax((size_t)L.ndr, 0);
+    for (const auto &r : runs) {
+        const int di = drain_index(r[0]);
+        L.tab[(size_t)di * (size_t)L.nrp + (size_t)r[1]] = (uint8_t)r[2];
+        kmax[(size_t)di] = std::max(kmax[(size_t)di], r[2]);
+    }
+    for (int x : kmax) L.trips += x <= 4 ? 1 : (x + 7) / 8;
+    L.bytes = (size_t)8 * (size_t)L.slots + L.tab.size();
+    if (L.tab.size() > (size_t)kRowspanMaxTab || L.bytes > cap_bytes) return false;
+    // every entry's destination slot
+    for (int k = 0; k < nr; k++) {
+        const RsRow &R = L.rows[(size_t)step(k)];
+        int ld = L.lead[(size_t)k], rn = R.run0;
+        bool in = false;
+        for (uint32_t e = ptr[r0 + k]; e < ptr[r0 + k + 1]; e++) {
+            const int32_t c = col[e];
+            int16_t &dst = L.dest[(size_t)(e - ptr[r0])];
+            if (c >= r0 && c < r1) dst = (int16_t)(R.base + (step(c - r0) - R.first)), in = true;
+            else dst = (int16_t)(in ? rn++ : ld++);
+        }
+    }
+    return true;
+}
+// the bytes of a launch image that hold slots: its value and column arrays (SweepLds)
+static size_t rowspan_cap_bytes(int cap);
+// what mark_dataflow collects for the blocks it puts on the row-span loop, and the upload
+struct RsOut {
+    std::vector<int16_t> *code = nullptr;  // [2]: DFactor::ucode's host copies (the destinations go there)
+    const uint32_t *code0 = nullptr;       // [2]
+    size_t cap_bytes = 0;
+    std::vector<int16_t> lead;
+    std::vector<RsBlk> blk[2];
+    std::vector<RsRow> row[2];
+    std::vector<std::vector<uint8_t>> tab[2];  // per block
+    std::vector<int32_t> cap;
+    bool any = false;
+};
+static void upload_rowspan(DFactor &d, std::vector<int16_t> (&code)[2], RsOut &rs, int64_t ub0) {
+    d.urlead.release();
+    for (int dir = 0; dir < 2; dir++) d.urblk[dir].release(), d.urrow[dir].release(), d.urtab[dir].release();
+    d.hrs_cap.clear(), d.ublk0 = ub0;
+    d.ucode[0].upload(code[0]), d.ucode[1].upload(code[1]);
+    if (!rs.any) return;
+    for (int dir = 0; dir < 2; dir++) {
+        std::vector<uint8_t> tab;
+        for (size_t b = 0; b < rs.blk[dir].size(); b++) {
+            rs.blk[dir][b].tab = (uint32_t)tab.size();
+            tab.insert(tab.end(), rs.tab[dir][b].begin(), rs.tab[dir][b].end());
+        }
+        tab.resize(tab.size() + 2 * kRowspanMaxTab, 0);  // clamped table loads read past a block's own
+        d.urblk[dir].upload(rs.blk[dir]), d.urrow[dir].upload(rs.row[dir]), d.urtab[dir].upload(tab);
+    }
+    d.urlead.upload(rs.lead);
+    d.hrs_cap = rs.cap;
+}
+void rowspan_export(const Factor &f, const Schedule &s, int64_t block, int dir, int64_t cap_entries, int sched_cap,
+                    RsExport &out) {
+    out = RsExport{};
+    const int64_t nblk = (int64_t)s.blk_lvl.size() - 1;
+    if (block < 0 || block >= nblk || dir < 0 || dir > 1) throw Error(CPK_ERR_ARGS, "rowspan_export: bad block or direction");
+    const int64_t r0 = s.lvl_row[s.blk_lvl[block]], r1 = s.lvl_row[s.blk_lvl[block + 1]];
+    const int nr = (int)(r1 - r0);
+    out.r0 = r0, out.nr = nr;
+    auto K = [&](int64_t q) { return (int64_t)s.order[(size_t)q]; };
+    // the block's rows in the device layout's entry order (make_dfactor): forward rows by
+    // ascending key of the column, backward rows (columns of L) by descending key of the row
+    std::vector<std::vector<std::tuple<int64_t, int32_t, double>>> rows((size_t)nr);
+    if (dir == 0) {
+        for (int64_t c = 0; c < r1; c++)
+            for (int64_t p = f.Lp[c]; p < f.Lp[c + 1]; p++)
+                if (f.Li[p] >= r0 && f.Li[p] < r1) rows[(size_t)(f.Li[p] - r0)].push_back({K(c), (int32_t)c, f.Lx[p]});
+    } else {
+        for (int64_t j = r0; j < r1; j++)
+            for (int64_t p = f.Lp[j]; p < f.Lp[j + 1]; p++) rows[(size_t)(j - r0)].push_back({-K(f.Li[p]), f.Li[p], f.Lx[p]});
+    }
+    std::vector<uint32_t> ptr((size_t)r1 + 1, 0);
+    out.rowptr.assign((size_t)nr + 1, 0);
+    for (int k = 0; k < nr; k++) {
+        std::sort(rows[(size_t)k].begin(), rows[(size_t)k].end(), [](auto &x, auto &y) { return std::get<0>(x) < std::get<0>(y); });
+        out.rowptr[(size_t)k + 1] = out.rowptr[(size_t)k] + (int64_t)rows[(size_t)k].size();
+        for (auto &e : rows[(size_t)k]) out.col.push_back(std::get<1>(e)), out.val.push_back(std::get<2>(e));
+    }
+    out.ne = (int64_t)out.col.size();
+    for (int64_t r = r0; r <= r1; r++) ptr[(size_t)r] = (uint32_t)out.rowptr[(size_t)(r - r0)];
+    // rowspan_layout indexes the column array by ptr: entries of rows before r0 are none (ptr 0)
+    std::vector<std::pair<int64_t, int32_t>> order;
+    for (int k = 0; k < nr; k++) order.push_back({K(r0 + k), k});
+    std::sort(order.begin(), order.end());
+    out.step.assign((size_t)nr, 0);
+    for (int t = 0; t < nr; t++) out.step[(size_t)order[(size_t)t].second] = dir ? nr - 1 - t : t;
+    RsLayout L;
+    const size_t cap = rowspan_cap_bytes((int)(cap_entries > 0 ? cap_entries : sched_cap));
+    out.eligible = rowspan_layout((int)r0, (int)r1, ptr, out.col, [&](int k) { return (int)out.step[(size_t)k]; }, cap, L);
+    if (!out.eligible) return;
+    out.slots = L.slots, out.ndr = L.ndr, out.nrp = L.nrp, out.trips = L.trips;
+    out.dset[0] = L.dset[0], out.dset[1] = L.dset[1];
+    out.dest.assign(L.dest.begin(), L.dest.end()), out.lead.assign(L.lead.begin(), L.lead.end());
+    out.rows = L.rows, out.tab = L.tab;
+}
+
 void mark_dataflow(std::vector<int32_t> &meta, const std::vector<int64_t> &round_ptr, const std::vector<uint32_t> &fptr,
                    const std::vector<int32_t> &fcol, const std::vector<uint32_t> &bptr, const std::vector<int32_t> &bcol,
                    int mode, int cs_mode, const std::vector<int16_t> &ustep, int64_t urow0,
-                   std::vector<int64_t> *model) {
+                   std::vector<int64_t> *model, int rs_mode = 1, RsOut *rs = nullptr) {
     if (model) model->clear();
     if (round_ptr.size() < 3) return;
     const int64_t b0 = round_ptr[1], b1 = round_ptr.back();  // the upper rounds
+    const bool rs_on = rs && rs_mode != 1 && !ustep.empty();
+    if (rs_on) {
+        rs->lead.assign(ustep.size(), 0), rs->cap.assign((size_t)(b1 - b0), 0);
+        for (int dir = 0; dir < 2; dir++) {
+            rs->blk[dir].assign((size_t)(b1 - b0), RsBlk{0, 0, 0, 0, 0, 0, 0});
+            rs->row[dir].assign(ustep.size() / 2, RsRow{0, 0, 0, 0, 0, 0});
+            rs->tab[dir].assign((size_t)(b1 - b0), {});
+        }
+    }
+    std::atomic<bool> rs_any{false};
+    // the image a row-span block may fill: a round of many blocks is launched with an image sized
+    // to its own largest block (launch_img: more workgroups share a CU), and a row-span block must
+    // not make that image grow -- its slots and table fit what the round's largest entry count
+    // already asks for; a narrow round (the chain's, or resident at once) has the kernel's image
+    std::vector<size_t> round_cap(round_ptr.size() - 1, rs_on ? rs->cap_bytes : 0);
+    if (rs_on)
+        for (size_t r = 1; r + 1 < round_ptr.size(); r++) {
+            if (round_ptr[r + 1] - round_ptr[r] <= kRowspanNarrowRound) continue;
+            int cap = 1;
+            for (int64_t b = round_ptr[r]; b < round_ptr[r + 1]; b++)
+                cap = std::max({cap, meta[(size_t)b * 8 + 5] - meta[(size_t)b * 8 + 4], meta[(size_t)b * 8 + 7] - meta[(size_t)b * 8 + 6]});
+            round_cap[r] = std::min(round_cap[r], rowspan_cap_bytes(cap));
+        }
     // per block and direction: nr, level trips, dataflow trips, outside terms behind in-block
-    // ones, column sweep valid, flags chosen (cpk_debug_block_model: the loops' cost model)
+    // ones, column sweep valid, loop chosen, row-span eligible, its drain trips
+    // (cpk_debug_block_model: the loops' cost model)
     if (model) model->assign((size_t)(b1 - b0) * 2 * kBlockModelW, -1);
     const double alpha = kDataflowTripCost;
     const bool df_on = CPK_UPPER_DATAFLOW && mode != 1;
@@ -363,6 +570,8 @@ void mark_dataflow(std::vector<int32_t> &meta, const std::vector<int64_t> &round
                     drain = drain || t > step(k);
                 }
                 cs_valid = cs_valid && !(drain && maxrun > 127);  // kCsRunMax: a run's length in its staged column
+                // the price of the loop chosen so far: the level or dataflow loop, then the column sweep
+                double chosen = df ? kDataflowTripCycles[dir] * (double)dt : kLevelTripCycles * (double)lt;
                 if (cs_valid) {
                     const int rpl = std::min((nr + kWave - 1) / kWave, 4);
                     int64_t trips = 0;  // drain trips: four terms of every row's run per trip
@@ -370,10 +579,49 @@ void mark_dataflow(std::vector<int32_t> &meta, const std::vector<int64_t> &round
                         for (int x : run) trips += (x + 3) / 4;
                     const double ct = (double)nr * (drain ? kColsweepStepDrainCycles : kColsweepStepCycles)[rpl - 1] +
                                       (double)trips * kColsweepDrainCycles[rpl - 1];
-                    const double base = df ? kDataflowTripCycles[dir] * (double)dt : kLevelTripCycles * (double)lt;
-                    cs = cs_mode == 2 || ct < base;
+                    cs = cs_mode == 2 || ct < chosen;
+                    if (cs) chosen = ct;
                 }
-                if (cs) m[3] |= (dir ? kMetaCsBwd : kMetaCsFwd) | (drain ? (dir ? kMetaCoBwd : kMetaCoFwd) : 0);
+                // the row-span loop (levels_rowspan): a step per row and a trip per drain step (two
+                // where a run is longer than eight), plus what its staging costs over the other
+                // loops'; chosen against the loop picked so far.  A loop forced by all_dataflow or
+                // all_colsweep stays forced unless all_rowspan is set as well
+                const bool forced_other = mode == 2 || cs_mode == 2;
+                bool rsp = false;
+                int64_t rs_ok = rs_on ? 0 : -1, rs_trips = -1;
+                if (rs_on && nr <= kRowspanMaxRows) {
+                    RsLayout L;
+                    const size_t rnd = (size_t)(std::upper_bound(round_ptr.begin(), round_ptr.end(), b) - round_ptr.begin()) - 1;
+                    if (rowspan_layout(r0, r1, ptr, col, step, round_cap[std::min(rnd, round_cap.size() - 1)], L)) {
+                        rs_ok = 1, rs_trips = L.trips;
+                        // (the staging's extra cost counts in a wide round, where blocks run for throughput; a
+                        // narrow round's blocks are chained tasks whose staging overlaps their wait, and the
+                        // level phase is what the next task waits for)
+                        const bool narrow = round_ptr[rnd + 1] - round_ptr[rnd] <= kRowspanNarrowRound;
+                        const double rt = kRowspanBaseCycles + (narrow ? 0.0 : kRowspanStagingCycles) +
+                                          (double)nr * kRowspanStepCycles[nr > kWave] + (double)L.trips * kRowspanDrainCycles;
+                        rsp = rs_mode == 2 || (!forced_other && rt < chosen);
+                        if (rsp) {
+                            // the block record, the rows by step, the destinations in place of the codes
+                            RsBlk &B = rs->blk[dir][(size_t)(b - b0)];
+                            B.dlo = L.dset[0], B.dhi = L.dset[1], B.slots = (uint16_t)L.slots, B.ndr = (uint16_t)L.ndr;
+                            B.nrp = (uint32_t)L.nrp;
+                            for (int s = 0; s < nr; s++) rs->row[dir][(size_t)(r0 - urow0 + s)] = L.rows[(size_t)s];
+                            for (int k = 0; k < nr; k++) rs->lead[(size_t)(2 * (r0 + k - urow0) + dir)] = L.lead[(size_t)k];
+                            std::copy(L.dest.begin(), L.dest.end(), rs->code[dir].begin() + (ptr[r0] - rs->code0[dir]));
+                            rs->tab[dir][(size_t)(b - b0)] = std::move(L.tab);
+                            // the entries an image must hold for this block: 10 bytes each (SweepLds)
+                            const int32_t need = (int32_t)((L.bytes + 9) / 10);
+                            int32_t &cp = rs->cap[(size_t)(b - b0)];  // (both directions of a block run on one thread)
+                            cp = std::max(cp, need);
+                            rs_any = true;
+                        }
+                    }
+                }
+                // a row-span block carries the column sweep's flag too (the kernels then load its
+                // steps and staged columns) and is told apart by its RsBlk record
+                if (rsp) m[3] |= dir ? kMetaCsBwd : kMetaCsFwd;
+                else if (cs) m[3] |= (dir ? kMetaCsBwd : kMetaCsFwd) | (drain ? (dir ? kMetaCoBwd : kMetaCoFwd) : 0);
                 else if (df) m[3] |= dir ? kMetaDfBwd : kMetaDfFwd;
                 if (model) {
                     int64_t *o = &(*model)[(size_t)(((b - b0) * 2 + dir) * kBlockModelW)];
@@ -381,11 +629,13 @@ void mark_dataflow(std::vector<int32_t> &meta, const std::vector<int64_t> &round
                     for (int k = 0; k < nr; k++)
                         for (int c : terms[k]) outs += c < 0;
                     o[0] = b, o[1] = dir, o[2] = nr, o[3] = lt, o[4] = df_on ? dt : -1, o[5] = outs, o[6] = cs_valid,
-                    o[7] = cs ? (drain ? 3 : 2) : (df ? 1 : 0);
+                    o[7] = rsp ? 4 : cs ? (drain ? 3 : 2) : (df ? 1 : 0);
+                    o[8] = rs_ok, o[9] = rs_trips;
                 }
             }
         }
     }, 4);
+    if (rs_on) rs->any = rs_any;
 }
 
 static void build_chain(DFactor &d, const std::vector<int32_t> &meta, const std::vector<uint32_t> &fptr,
@@ -552,8 +802,12 @@ void make_dfactor(const Factor &f, const Schedule &s, DFactor &d, const std::vec
         m[4] = (int32_t)fptr[r0], m[5] = (int32_t)fptr[r1], m[6] = (int32_t)bptr[r0], m[7] = (int32_t)bptr[r1];
     }
     {
-        const std::vector<int16_t> us = build_ufold(d, meta, s.round_ptr, fptr, fcol, bptr, bcol, [&](int64_t q) { return K(q); });
-        mark_dataflow(meta, s.round_ptr, fptr, fcol, bptr, bcol, d.dataflow, d.colsweep, us, d.urow0, &d.hmodel);
+        std::vector<int16_t> code[2];
+        const std::vector<int16_t> us = build_ufold(d, meta, s.round_ptr, fptr, fcol, bptr, bcol, [&](int64_t q) { return K(q); }, code);
+        RsOut rs;
+        rs.code = code, rs.code0 = d.ucode0, rs.cap_bytes = rowspan_cap_bytes(d.sweep_cap[1]);
+        mark_dataflow(meta, s.round_ptr, fptr, fcol, bptr, bcol, d.dataflow, d.colsweep, us, d.urow0, &d.hmodel, d.rowspan, &rs);
+        upload_rowspan(d, code, rs, s.round_ptr.size() >= 3 ? s.round_ptr[1] : 0);
     }
     d.meta.upload(meta);
     d.hmeta = meta;
@@ -1213,6 +1467,7 @@ void dsep_sweep_setup(Ctx &c, DSep &T, const RankPlan &rp, int P) {
     d.pipelined = true, d.no_upper = false, d.no_col16 = true, d.fuse_last = false, d.skip0 = false;
     d.dataflow = c.opts.no_dataflow ? 1 : (c.opts.all_dataflow ? 2 : 0);
     d.colsweep = c.opts.no_colsweep ? 1 : (c.opts.all_colsweep ? 2 : 0);
+    d.rowspan = c.opts.no_rowspan ? 1 : (c.opts.all_rowspan ? 2 : 0);
     d.N = NT;
     std::vector<uint32_t> fptr((size_t)NT + 1, 0), bptr((size_t)NT + 1, 0);
     std::vector<int32_t> fcol, bcol, perm((size_t)NT, 0);
@@ -1252,9 +1507,13 @@ void dsep_sweep_setup(Ctx &c, DSep &T, const RankPlan &rp, int P) {
     }
     {
         // row base + k is T row S.order[k]: its entries are in T's order (mark_dataflow checks it)
+        std::vector<int16_t> code[2];
         const std::vector<int16_t> us = build_ufold(d, meta, S.round_ptr, fptr, fcol, bptr, bcol,
-                    [&](int64_t q) { return q < base ? q - base : (int64_t)S.order[(size_t)(q - base)]; });
-        mark_dataflow(meta, S.round_ptr, fptr, fcol, bptr, bcol, d.dataflow, d.colsweep, us, d.urow0, nullptr);
+                    [&](int64_t q) { return q < base ? q - base : (int64_t)S.order[(size_t)(q - base)]; }, code);
+        RsOut rs;
+        rs.code = code, rs.code0 = d.ucode0, rs.cap_bytes = rowspan_cap_bytes(d.sweep_cap[1]);
+        mark_dataflow(meta, S.round_ptr, fptr, fcol, bptr, bcol, d.dataflow, d.colsweep, us, d.urow0, &d.hmodel, d.rowspan, &rs);
+        upload_rowspan(d, code, rs, S.round_ptr.size() >= 3 ? S.round_ptr[1] : 0);
     }
     for (size_t r = 0; r < d.round_fits.size(); r++)
         for (int64_t b = S.round_ptr[r]; b < S.round_ptr[r + 1]; b++) {
@@ -1438,6 +1697,7 @@ __host__ __device__ constexpr size_t sweep_lds_bytes_dev(int R, int CAP) {
     return ((size_t)8 * (R + 1) + 10 * ((size_t)CAP + kSweepPad) + 6 * ((size_t)R + 1) + 15) & ~(size_t)15;
 }
 size_t sweep_lds_bytes(int R, int CAP) { return sweep_lds_bytes_dev(R, CAP); }
+static size_t rowspan_cap_bytes(int cap) { return (size_t)10 * ((size_t)cap + kSweepPad); }
 
 // Outside-block prefix: a row's leading terms that refer to rows finished by earlier launches
 // are already products in LDS (c < 0).  Subtracting them here, every row at once, takes them
@@ -1510,6 +1770,12 @@ struct UFold {
     int32_t row0 = 0;
     const int16_t *cf = nullptr, *cb = nullptr;  // DFactor::ucode, forward / backward
     uint32_t cf0 = 0, cb0 = 0;
+    // the row-span loop's layout (DFactor::urlead, urblk, urrow, urtab; null: no block is on it)
+    const int16_t *rl = nullptr;
+    const RsBlk *rb[2] = {nullptr, nullptr};
+    const RsRow *rr[2] = {nullptr, nullptr};
+    const uint8_t *rt[2] = {nullptr, nullptr};
+    int64_t ub0 = 0;
 };
 // the image of a launch over blocks [b0, b1): their largest row count and entry count (either
 // direction), capped by the kernel's R / CAP.  A smaller image than the kernel's maximum lets
@@ -1521,6 +1787,8 @@ static Img launch_img(const DFactor &F, int64_t b0, int64_t b1, int rmax, int ca
         for (int64_t b = b0; b < b1; b++) {
             const int32_t *m = &F.hmeta[(size_t)b * 8];
             R = std::max(R, m[1] - m[0]), CAP = std::max({CAP, m[5] - m[4], m[7] - m[6]});
+            // a block on the row-span loop: its slots and run lengths (mark_dataflow)
+            if (b >= F.ublk0 && (size_t)(b - F.ublk0) < F.hrs_cap.size()) CAP = std::max(CAP, (int)F.hrs_cap[(size_t)(b - F.ublk0)]);
         }
         it = F.img_cache.emplace(std::make_pair(b0, b1), std::make_pair(R, CAP)).first;
     }
@@ -1529,8 +1797,13 @@ static Img launch_img(const DFactor &F, int64_t b0, int64_t b1, int rmax, int ca
 static size_t img_bytes(const Img &g) { return sweep_lds_bytes(g.R, g.CAP); }
 static inline UFold ufold_of(const DFactor &F) {
     const bool cs = F.ustep.n && F.ucode[0].n && F.ucode[1].n;
-    return UFold{F.ufold.n ? F.ufold.p : nullptr, cs ? F.ustep.p : nullptr, F.urow0, cs ? F.ucode[0].p : nullptr,
-                 cs ? F.ucode[1].p : nullptr, F.ucode0[0], F.ucode0[1]};
+    UFold u{F.ufold.n ? F.ufold.p : nullptr, cs ? F.ustep.p : nullptr, F.urow0, cs ? F.ucode[0].p : nullptr,
+            cs ? F.ucode[1].p : nullptr, F.ucode0[0], F.ucode0[1]};
+    if (cs && F.ufold.n && F.urlead.n) {
+        u.rl = F.urlead.p, u.ub0 = F.ublk0;
+        for (int dir = 0; dir < 2; dir++) u.rb[dir] = F.urblk[dir].p, u.rr[dir] = F.urrow[dir].p, u.rt[dir] = F.urtab[dir].p;
+    }
+    return u;
 }
 
 // The column sweep (one wave; forward and backward alike): the block's rows in the order of
@@ -1683,6 +1956,169 @@ __device__ __forceinline__ void colsweep_dispatch(SweepLds &S, int nr, int lane,
         else if (nr <= 2 * kWave) levels_colsweep<2, false>(S, nr, lane);
         else levels_colsweep<4, false>(S, nr, lane);
     }
+}
+
+// The row-span loop (one wave, at most two rows per lane; forward and backward alike): the column
+// sweep's schedule -- step t solves the row of step t and every row subtracts its in-block term of
+// column t -- on a dense image.  A row's in-block values sit at consecutive slots from its first
+// in-block step to its own, so the slot of step t is an address that advances by one per step: the
+// values of four steps are loaded at immediate offsets before the first of them runs, no step
+// waits on a load it issued, and no column code is read or compared.  Whether the row has a term
+// at step t is a bit of a mask it holds in registers; an absent term subtracts +0.0, never the
+// gap's content.  The outside products behind an in-block term (its run) are subtracted right
+// after that step, in the row's order: the steps that have any run are a wave-uniform bit set in
+// the block's record, so the drain is a scalar branch taken at those steps only, and each row's
+// run length there comes from a small table staged behind the slots.
+// Same terms, same order, product and subtraction rounded separately: bit-identical.
+template <int RPL>
+struct RsState {
+    double acc[RPL];
+    uint64_t m[RPL];                 // presence bits of the 64 steps under way, shifted as they pass
+    int a[RPL], lo[RPL], hi[RPL];    // slot of step 0 (base - first) and the clamp of a group's address
+    int rp[RPL];                     // the next run term
+};
+// one trip of a drain: W terms of every row's run, loads first; a term past the run subtracts +0.0
+template <int Q, int QE, int W, int RPL>  // rows Q .. QE - 1
+__device__ __forceinline__ void rowspan_trip(RsState<RPL> &st, const double *v, const int (&k)[2], int j0) {
+    double u[2][W];
+    {
+        const double *b = v + st.rp[Q] + min(j0, k[Q]);  // clamped to the run's end: inside the end guard
+#pragma unroll
+        for (int i = 0; i < W; i++) u[0][i] = b[i];
+    }
+    if constexpr (Q + 1 < QE) {
+        const double *b = v + st.rp[Q + 1] + min(j0, k[Q + 1]);
+#pragma unroll
+        for (int i = 0; i < W; i++) u[1][i] = b[i];
+    }
+    {
+        const int kk = k[Q] - j0;
+#pragma unroll
+        for (int i = 0; i < W; i++) st.acc[Q] = st.acc[Q] - (i < kk ? u[0][i] : 0.0);
+    }
+    if constexpr (Q + 1 < QE) {
+        const int kk = k[Q + 1] - j0;
+#pragma unroll
+        for (int i = 0; i < W; i++) st.acc[Q + 1] = st.acc[Q + 1] - (i < kk ? u[1][i] : 0.0);
+    }
+}
+template <int Q, int RPL>
+__device__ __forceinline__ void rowspan_drain(RsState<RPL> &st, const double *v, const uint8_t *tab, int lane) {
+    int k[2] = {0, 0};
+    k[Q] = tab[lane + Q * kWave];
+    if constexpr (Q + 1 < RPL) k[Q + 1] = tab[lane + (Q + 1) * kWave];
+    const int km = max(k[0], k[1]);
+    if (__any(km > 4)) {
+        // long runs sit on one or two rows of a step: eight terms a trip, a row at a time (both
+        // rows' sixteen values in flight would cost the kernel a wave of residency), and only the
+        // rows that still have terms
+        for (int j0 = 0; __any(j0 < k[Q]); j0 += 8) rowspan_trip<Q, Q + 1, 8>(st, v, k, j0);
+        if constexpr (Q + 1 < RPL)
+            for (int j0 = 0; __any(j0 < k[Q + 1]); j0 += 8) rowspan_trip<Q + 1, Q + 2, 8>(st, v, k, j0);
+    } else {
+        rowspan_trip<Q, RPL, 4>(st, v, k, 0);
+    }
+    st.rp[Q] += k[Q];
+    if constexpr (Q + 1 < RPL) st.rp[Q + 1] += k[Q + 1];
+}
+// the term of one row at one step: its product where the mask has the step, else +0.0
+__device__ __forceinline__ double rowspan_term(uint64_t m, int i, double v, double x) {
+    const double p = v * x;
+    return ((uint32_t)m >> i) & 1u ? p : 0.0;
+}
+// steps Q * 64 .. of the rows q >= Q, four steps to a group; dset: this half's drain steps;
+// tab: the run lengths of the next drain step.  Steps past the block's last have no mask bit and
+// no drain, so a last group runs whole.
+template <int Q, int RPL>
+__device__ __forceinline__ void rowspan_steps(RsState<RPL> &st, const double *v, int nr, uint64_t dset,
+                                              const uint8_t *&tab, int nrp, int lane) {
+    const int jn = min(kWave, nr - Q * kWave);
+    for (int j0 = 0; j0 < jn; j0 += 4) {
+        double u[2][4];
+        {
+            const double *b = v + min(max(st.a[Q] + Q * kWave + j0, st.lo[Q]), st.hi[Q]);
+#pragma unroll
+            for (int i = 0; i < 4; i++) u[0][i] = b[i];
+        }
+        if constexpr (Q + 1 < RPL) {
+            const double *b = v + min(max(st.a[Q + 1] + Q * kWave + j0, st.lo[Q + 1]), st.hi[Q + 1]);
+#pragma unroll
+            for (int i = 0; i < 4; i++) u[1][i] = b[i];
+        }
+        const uint32_t dg = (uint32_t)(dset >> j0) & 15u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const double x = lane_bcast(st.acc[Q], j0 + i);  // the row of this step: every term taken
+            st.acc[Q] = st.acc[Q] - rowspan_term(st.m[Q], i, u[0][i], x);
+            if constexpr (Q + 1 < RPL) st.acc[Q + 1] = st.acc[Q + 1] - rowspan_term(st.m[Q + 1], i, u[1][i], x);
+            if (dg & (1u << i)) {
+                rowspan_drain<Q, RPL>(st, v, tab, lane);
+                tab += nrp;
+            }
+        }
+        st.m[Q] >>= 4;
+        if constexpr (Q + 1 < RPL) st.m[Q + 1] >>= 4;
+    }
+}
+template <int RPL>
+__device__ __forceinline__ void levels_rowspan(SweepLds &S, int nr, int lane, const RsRow (&rw)[2], const RsBlk &rb) {
+    RsState<RPL> st;
+    uint64_t mhi = 0;
+#pragma unroll
+    for (int q = 0; q < RPL; q++) {
+        const int t = lane + q * kWave;
+        const bool on = t < nr;
+        st.acc[q] = S.w[on ? S.lv[t] : 0];
+        st.m[q] = on ? rw[q].mlo : 0;
+        if (q == 1) mhi = on ? rw[q].mhi : 0;
+        // a row off the block reads the first guard; a group that meets no step of the row's span
+        // clamps to the span's ends, whose three slots either side are inside the image
+        st.a[q] = on ? rw[q].base - rw[q].first : 0;
+        st.lo[q] = on ? rw[q].base - 3 : 0;
+        st.hi[q] = on ? rw[q].base + (t - rw[q].first) : 0;
+        st.rp[q] = on ? rw[q].run0 : 0;
+    }
+    const uint8_t *tab = reinterpret_cast<const uint8_t *>(S.v + rb.slots);
+    const int nrp = (int)rb.nrp;
+    rowspan_steps<0, RPL>(st, S.v, nr, rb.dlo, tab, nrp, lane);
+    if constexpr (RPL > 1) {
+        st.m[1] = mhi;
+        rowspan_steps<1, RPL>(st, S.v, nr, rb.dhi, tab, nrp, lane);
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; q++) {
+        const int t = lane + q * kWave;
+        if (t < nr) S.w[S.lv[t]] = st.acc[q];
+    }
+}
+// the wave's rows by step (lane, lane + 64), loaded by the level wave itself
+__device__ __forceinline__ void rowspan_rows(const RsRow *rows, int nr, int lane, RsRow (&rw)[2]) {
+    rw[0] = rows[lane < nr ? lane : 0];
+    rw[1] = rows[lane + kWave < nr ? lane + kWave : 0];
+}
+// the rows' first run slots alone: read with the block's other static loads, which also brings the
+// records' lines on chip for rowspan_rows
+__device__ __forceinline__ void rowspan_run0(const RsRow *rows, int nr, int lane, int (&run0)[2]) {
+    run0[0] = rows[lane < nr ? lane : 0].run0;
+    run0[1] = rows[lane + kWave < nr ? lane + kWave : 0].run0;
+}
+__device__ __forceinline__ void rowspan_dispatch(SweepLds &S, int nr, int lane, const RsRow (&rw)[2], const RsBlk &rb) {
+    if (nr <= kWave) levels_rowspan<1>(S, nr, lane, rw, rb);
+    else levels_rowspan<2>(S, nr, lane, rw, rb);
+}
+// the block's record (one uniform load; slots == 0: not on the loop)
+__device__ __forceinline__ RsBlk rowspan_record(const UFold &uf, bool bwd, int64_t b) {
+    RsBlk r{0, 0, 0, 0, 0, 0, 0};
+    if (uf.rb[bwd] && b >= uf.ub0) {  // (not behind the block record's flags: the two loads go out together)
+        // wave-uniform by construction; read through the first lane so the drain test is a scalar branch
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(uf.rb[bwd] + (b - uf.ub0));
+        uint32_t x[7];
+#pragma unroll
+        for (int i = 0; i < 7; i++) x[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[i]);
+        r.dlo = x[0] | (uint64_t)x[1] << 32, r.dhi = x[2] | (uint64_t)x[3] << 32;
+        r.tab = x[4], r.slots = (uint16_t)(x[5] & 0xffffu), r.ndr = (uint16_t)(x[5] >> 16), r.nrp = x[6];
+    }
+    return r;
 }
 
 // The level phase, out of LDS.  Per level every thread takes whole rows and consumes a row's
@@ -2192,10 +2628,15 @@ __device__ __forceinline__ void upper_block(
     const int tid = threadIdx.x;
     // the column sweep for this block and direction (mark_dataflow); it needs the step table
     const bool cs = uf.s != nullptr && (m.l1 & (BWD ? kMetaCsBwd : kMetaCsFwd));
+    // ... or the row-span loop: the block's record says so (its staged columns are slots then)
+    static_assert(TPB * 8 >= kRowspanMaxTab && TPB * 8 <= 2 * kRowspanMaxTab,
+                  "two words of the run lengths per thread, read inside urtab's padding (upload_rowspan)");
+    const RsBlk rbk = rowspan_record(uf, BWD, b);
+    const bool rs = cs && rbk.slots != 0;
     SweepLds S(smem, R, CAP);
     (void)CAP;
     uint32_t q[RPU];
-    int32_t sp[RPU], fo[RPU], st[RPU];
+    int32_t sp[RPU], fo[RPU], st[RPU], ld[RPU];
     double a[RPU], d[RPU];
     int32_t c[EPU];
     double v[EPU], g[EPU];
@@ -2205,6 +2646,7 @@ __device__ __forceinline__ void upper_block(
         q[j] = ptr[rr], sp[j] = (BWD ? out != nullptr : !sched_in) ? perm[rr] : rr;
         fo[j] = uf.p ? uf.p[2 * (rr - uf.row0) + (BWD ? 1 : 0)] : 0;
         st[j] = cs ? uf.s[2 * (rr - uf.row0) + (BWD ? 1 : 0)] : 0;
+        ld[j] = cs && uf.rl ? uf.rl[2 * (rr - uf.row0) + (BWD ? 1 : 0)] : 0;
         if (BWD) d[j] = D[rr];
     }
 #pragma unroll
@@ -2214,16 +2656,36 @@ __device__ __forceinline__ void upper_block(
         c[u] = __builtin_nontemporal_load(col + ec), v[u] = __builtin_nontemporal_load(val + ec);
     }
     // staged columns (static: before the wait): local row, or the layout's code (column sweep; lv
-    // holds the rows by step); R outside
+    // holds the rows by step; its loads go out with the entries', not behind their columns); R outside
     int32_t cl[EPU];
+    if (cs) {
 #pragma unroll
-    for (int u = 0; u < EPU; u++) {
-        const bool local = c[u] >= r0 && c[u] < r1;
-        const uint32_t ec = e0 + (uint32_t)(tid + u * TPB < ne ? tid + u * TPB : 0);
-        cl[u] = cs ? (int32_t)(uint16_t)(BWD ? uf.cb[ec - uf.cb0] : uf.cf[ec - uf.cf0]) : (!local ? R : c[u] - r0);
+        for (int u = 0; u < EPU; u++) {
+            const uint32_t ec = e0 + (uint32_t)(tid + u * TPB < ne ? tid + u * TPB : 0);
+            cl[u] = (int32_t)(uint16_t)(BWD ? uf.cb[ec - uf.cb0] : uf.cf[ec - uf.cf0]);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < EPU; u++) cl[u] = !(c[u] >= r0 && c[u] < r1) ? R : c[u] - r0;
+    }
+    int run0[2] = {0, 0};
+    if (rs && tid < kWave) {  // (both in one register: a second one costs the backward kernel a wave of residency)
+        rowspan_run0(uf.rr[BWD ? 1 : 0] + (r0 - uf.row0), nr, tid, run0);
+        run0[0] |= run0[1] << 16;
     }
     if (!cs)
         for (int l = tid; l <= nl; l += TPB) S.lv[l] = (int16_t)(lvl_row[m.l0 + l] - r0);
+    if (rs) {
+        // the run lengths of a row-span block (at most kRowspanMaxTab bytes) go behind the slots
+        // now, while the image is still unused: held in registers they would sit on top of the
+        // staging's peak
+        const int ntb = (int)rbk.ndr * (int)rbk.nrp / 4;
+        const uint32_t *t32 = reinterpret_cast<const uint32_t *>(uf.rt[BWD ? 1 : 0] + rbk.tab);
+        uint32_t *l32 = reinterpret_cast<uint32_t *>(S.v + rbk.slots);
+        const uint32_t t0 = t32[tid], t1 = t32[tid + TPB];
+        if (tid < ntb) l32[tid] = t0;
+        if (tid + TPB < ntb) l32[tid + TPB] = t1;
+    }
 #pragma unroll
     for (int j = 0; j < RPU; j++) {
         if (!BWD) a[j] = xin[sp[j]];
@@ -2239,22 +2701,32 @@ __device__ __forceinline__ void upper_block(
     for (int j = 0; j < RPU; j++) {
         const int i = tid + j * TPB;
         if (i < nr) {
-            S.p[i] = (int16_t)(q[j] - e0);
-            if (uf.p) S.ps[i] = (int16_t)(q[j] - e0 + fo[j]);
+            const int p0 = rs ? ld[j] : (int)(q[j] - e0);  // row-span: the row's leads have slots of their own
+            S.p[i] = (int16_t)p0;
+            if (uf.p) S.ps[i] = (int16_t)(p0 + fo[j]);
             if (cs) S.lv[st[j]] = (int16_t)i;
             S.w[i] = BWD ? a[j] / d[j] : ((sp[j] >= neg_from) ? -a[j] : a[j]);
             if (!BWD && xs) xs[r0 + i] = S.w[i];
         }
     }
     if (tid == 0) S.p[nr] = (int16_t)ne, S.w[R] = 1.0;
-    if (tid < kSweepPad) S.c[ne + tid] = (int16_t)R;
+    if (tid < kSweepPad && !rs) S.c[ne + tid] = (int16_t)R;
+    if (rs) {  // row-span: every entry to its slot, no column (a loop of its own: one loop with
+               // both forms of the store costs the kernel a wave of residency)
 #pragma unroll
-    for (int u = 0; u < EPU; u++) {
-        const int e = tid + u * TPB;
-        if (e < ne) {
-            const bool local = c[u] >= r0 && c[u] < r1;
-            S.c[e] = (int16_t)cl[u];  // outside: R, pre-multiplied against the 1.0 slot
-            S.v[e] = local ? v[u] : v[u] * g[u];
+        for (int u = 0; u < EPU; u++) {
+            const int e = tid + u * TPB;
+            if (e < ne) S.v[cl[u]] = (c[u] >= r0 && c[u] < r1) ? v[u] : v[u] * g[u];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < EPU; u++) {
+            const int e = tid + u * TPB;
+            if (e < ne) {
+                const bool local = c[u] >= r0 && c[u] < r1;
+                S.c[e] = (int16_t)cl[u];  // outside: R, pre-multiplied against the 1.0 slot
+                S.v[e] = local ? v[u] : v[u] * g[u];
+            }
         }
     }
     __syncthreads();
@@ -2266,7 +2738,14 @@ __device__ __forceinline__ void upper_block(
     // (a single wave's LDS accesses complete in program order) the chain is LDS latency only;
     // narrow levels give each row a lane group (levels_grouped)
     if (tid < kWave) {
-        if (cs) colsweep_dispatch(S, nr, tid, m.l1 & (BWD ? kMetaCoBwd : kMetaCoFwd));
+        if (rs) {
+            // the rows' records now (held across the staging they would cost a wave of residency);
+            // their lines are on the way since the run slots were read
+            RsRow rw[2];
+            rowspan_rows(uf.rr[BWD ? 1 : 0] + (r0 - uf.row0), nr, tid, rw);
+            rw[0].run0 = run0[0] & 0xffff, rw[1].run0 = run0[0] >> 16;
+            rowspan_dispatch(S, nr, tid, rw, rbk);
+        } else if (cs) colsweep_dispatch(S, nr, tid, m.l1 & (BWD ? kMetaCoBwd : kMetaCoFwd));
         else if (CPK_UPPER_DATAFLOW && (m.l1 & (BWD ? kMetaDfBwd : kMetaDfFwd)))
             levels_dataflow<BWD, CPK_DF_CH(BWD), true, RMAX / kWave>(S, nr, R, ne, tid);
         else if (CPK_UPPER_GROUP(BWD)) levels_grouped<CPK_UPPER_CH(BWD), BWD, true>(S, nl, false, tid);
@@ -2325,7 +2804,7 @@ __device__ __forceinline__ void last_block(
     const uint32_t *__restrict__ fptr, const int32_t *__restrict__ fcol, const double *__restrict__ fval,
     const uint32_t *__restrict__ bptr, const int32_t *__restrict__ bcol, const double *__restrict__ bval,
     const double *__restrict__ D, const int32_t *__restrict__ perm, const double *__restrict__ xin, int64_t neg_from,
-    int sched_in, double *xs, double *w, double *out, double *ys, const UFold &uf, const Img &img,
+    int sched_in, double *xs, double *w, double *out, double *ys, const UFold &uf, int64_t b, const Img &img,
     const Wait &wait = Wait{}) {
     constexpr int RMAX = RPU * TPB;
     const int R = img.R, CAP = img.CAP;
@@ -2333,10 +2812,15 @@ __device__ __forceinline__ void last_block(
     const int nef = m.fe1 - m.fe0, neb = m.be1 - m.be0;
     const int tid = threadIdx.x;
     const bool csf = uf.s != nullptr && (m.l1 & kMetaCsFwd), csb = uf.s != nullptr && (m.l1 & kMetaCsBwd);
+    // the row-span loop per direction (the block's records; upper_block)
+    static_assert(TPB * 8 >= kRowspanMaxTab && TPB * 8 <= 2 * kRowspanMaxTab,
+                  "two words of the run lengths per thread, read inside urtab's padding (upload_rowspan)");
+    const RsBlk rbf = rowspan_record(uf, false, b), rbb = rowspan_record(uf, true, b);
+    const bool rsf = csf && rbf.slots != 0, rsb = csb && rbb.slots != 0;
     SweepLds S(smem, R, CAP);
     (void)CAP;
     uint32_t qf[RPU], qb[RPU];
-    int32_t sp[RPU], dp[RPU], fof[RPU], fob[RPU], stf[RPU], stb[RPU];
+    int32_t sp[RPU], dp[RPU], fof[RPU], fob[RPU], stf[RPU], stb[RPU], ldf[RPU], ldb[RPU];
     double a[RPU], d[RPU];
     int32_t cf[EPU], cb[EPU];
     double vf[EPU], vb[EPU], g[EPU];
@@ -2346,6 +2830,7 @@ __device__ __forceinline__ void last_block(
         qf[j] = fptr[rr], qb[j] = bptr[rr], d[j] = D[rr];
         fof[j] = uf.p ? uf.p[2 * (rr - uf.row0)] : 0, fob[j] = uf.p ? uf.p[2 * (rr - uf.row0) + 1] : 0;
         stf[j] = csf ? uf.s[2 * (rr - uf.row0)] : 0, stb[j] = csb ? uf.s[2 * (rr - uf.row0) + 1] : 0;
+        ldf[j] = csf && uf.rl ? uf.rl[2 * (rr - uf.row0)] : 0, ldb[j] = csb && uf.rl ? uf.rl[2 * (rr - uf.row0) + 1] : 0;
         sp[j] = sched_in ? rr : perm[rr];
         dp[j] = out ? perm[rr] : rr;
     }
@@ -2364,6 +2849,21 @@ __device__ __forceinline__ void last_block(
     }
     if (!csf)
         for (int l = tid; l <= nl; l += TPB) S.lv[l] = (int16_t)(lvl_row[m.l0 + l] - r0);
+    // the run lengths of a row-span block, per direction, and (below) the rows' records: all
+    // loaded with the block's static loads and held -- this kernel and the chain run one
+    // workgroup per CU and every load they issue late is on a chained task's critical path
+    // (loading them after the staging as upper_block does, together with pricing the staging in
+    // the chained rounds, took the +-64 window from 488 to 482 it/s; the two were not separated)
+    uint32_t tbf[2] = {0, 0}, tbb[2] = {0, 0};
+    const int ntf = rsf ? (int)rbf.ndr * (int)rbf.nrp / 4 : 0, ntb = rsb ? (int)rbb.ndr * (int)rbb.nrp / 4 : 0;
+    if (rsf) {
+        const uint32_t *t32 = reinterpret_cast<const uint32_t *>(uf.rt[0] + rbf.tab);
+        tbf[0] = t32[tid], tbf[1] = t32[tid + TPB];
+    }
+    if (rsb) {
+        const uint32_t *t32 = reinterpret_cast<const uint32_t *>(uf.rt[1] + rbb.tab);
+        tbb[0] = t32[tid], tbb[1] = t32[tid + TPB];
+    }
 #pragma unroll
     for (int j = 0; j < RPU; j++) a[j] = xin[sp[j]];
     wait();
@@ -2382,29 +2882,38 @@ __device__ __forceinline__ void last_block(
     for (int j = 0; j < RPU; j++) {
         const int i = tid + j * TPB;
         if (i < nr) {
-            S.p[i] = (int16_t)(qf[j] - (uint32_t)m.fe0);
-            if (uf.p) S.ps[i] = (int16_t)(qf[j] - (uint32_t)m.fe0 + fof[j]);
+            const int p0 = rsf ? ldf[j] : (int)(qf[j] - (uint32_t)m.fe0);
+            S.p[i] = (int16_t)p0;
+            if (uf.p) S.ps[i] = (int16_t)(p0 + fof[j]);
             if (csf) S.lv[stf[j]] = (int16_t)i;
             S.w[i] = (sp[j] >= neg_from) ? -a[j] : a[j];
             if (xs) xs[r0 + i] = S.w[i];
         }
     }
     if (tid == 0) S.p[nr] = (int16_t)nef, S.w[R] = 1.0;
-    if (tid < kSweepPad) S.c[nef + tid] = (int16_t)R;
+    if (tid < kSweepPad && !rsf) S.c[nef + tid] = (int16_t)R;
+    if (rsf) {
+        uint32_t *t32 = reinterpret_cast<uint32_t *>(S.v + rbf.slots);
+        if (tid < ntf) t32[tid] = tbf[0];
+        if (tid + TPB < ntf) t32[tid + TPB] = tbf[1];
+    }
 #pragma unroll
     for (int u = 0; u < EPU; u++) {
         const int e = tid + u * TPB;
         if (e < nef) {
             const bool local = cf[u] >= r0 && cf[u] < r1;
-            S.c[e] = (int16_t)cl[u];
-            S.v[e] = local ? vf[u] : vf[u] * g[u];
+            if (!rsf) S.c[e] = (int16_t)cl[u];
+            S.v[rsf ? cl[u] : e] = local ? vf[u] : vf[u] * g[u];
         }
     }
+    RsRow rw[2];
+    if (rsf && tid < kWave) rowspan_rows(uf.rr[0] + (r0 - uf.row0), nr, tid, rw);
     __syncthreads();
     if (uf.p) fold_known<TPB>(S, nr, tid);
     else fold_prefix<TPB, 1>(S, nr, -1, R);
     if (tid < kWave) {
-        if (csf) colsweep_dispatch(S, nr, tid, m.l1 & kMetaCoFwd);
+        if (rsf) rowspan_dispatch(S, nr, tid, rw, rbf);
+        else if (csf) colsweep_dispatch(S, nr, tid, m.l1 & kMetaCoFwd);
         else if (CPK_UPPER_DATAFLOW && (m.l1 & kMetaDfFwd)) levels_dataflow<false, CPK_DF_CH(false), true, RMAX / kWave>(S, nr, R, nef, tid);
         else if (CPK_UPPER_GROUP(false)) levels_grouped<CPK_UPPER_CH(false), false, true>(S, nl, false, tid);
         else sweep_levels<kWave, false, true, CPK_UPPER_CH(false), true, true>(S, nl, false, tid);
@@ -2419,13 +2928,19 @@ __device__ __forceinline__ void last_block(
         const int i = tid + j * TPB;
         if (i < nr) {
             S.w[i] = S.w[i] / d[j];
-            S.p[i] = (int16_t)(qb[j] - (uint32_t)m.be0);
-            if (uf.p) S.ps[i] = (int16_t)(qb[j] - (uint32_t)m.be0 + fob[j]);
+            const int p0 = rsb ? ldb[j] : (int)(qb[j] - (uint32_t)m.be0);
+            S.p[i] = (int16_t)p0;
+            if (uf.p) S.ps[i] = (int16_t)(p0 + fob[j]);
             if (csb) S.lv[stb[j]] = (int16_t)i;
         }
     }
     if (tid == 0) S.p[nr] = (int16_t)neb;
-    if (tid < kSweepPad) S.c[neb + tid] = (int16_t)R;
+    if (tid < kSweepPad && !rsb) S.c[neb + tid] = (int16_t)R;
+    if (rsb) {
+        uint32_t *t32 = reinterpret_cast<uint32_t *>(S.v + rbb.slots);
+        if (tid < ntb) t32[tid] = tbb[0];
+        if (tid + TPB < ntb) t32[tid + TPB] = tbb[1];
+    }
     // the level loop needs the level bounds back if the forward loop took lv (flags or steps)
     if ((csf || (CPK_UPPER_DATAFLOW && (m.l1 & kMetaDfFwd))) && !csb && !(CPK_UPPER_DATAFLOW && (m.l1 & kMetaDfBwd)))
         for (int l = tid; l <= nl; l += TPB) S.lv[l] = (int16_t)(lvl_row[m.l0 + l] - r0);
@@ -2434,15 +2949,18 @@ __device__ __forceinline__ void last_block(
         const int e = tid + u * TPB;
         if (e < neb) {
             const bool local = cb[u] >= r0 && cb[u] < r1;
-            S.c[e] = csb ? uf.cb[(uint32_t)m.be0 + (uint32_t)e - uf.cb0] : (int16_t)(!local ? R : cb[u] - r0);
-            S.v[e] = local ? vb[u] : vb[u] * g[u];
+            const int16_t cd = csb ? uf.cb[(uint32_t)m.be0 + (uint32_t)e - uf.cb0] : (int16_t)(!local ? R : cb[u] - r0);
+            if (!rsb) S.c[e] = cd;
+            S.v[rsb ? (int)cd : e] = local ? vb[u] : vb[u] * g[u];
         }
     }
+    if (rsb && tid < kWave) rowspan_rows(uf.rr[1] + (r0 - uf.row0), nr, tid, rw);
     __syncthreads();
     if (uf.p) fold_known<TPB>(S, nr, tid);
     else fold_prefix<TPB, 1>(S, nr, -1, R);
     if (tid < kWave) {
-        if (csb) colsweep_dispatch(S, nr, tid, m.l1 & kMetaCoBwd);
+        if (rsb) rowspan_dispatch(S, nr, tid, rw, rbb);
+        else if (csb) colsweep_dispatch(S, nr, tid, m.l1 & kMetaCoBwd);
         else if (CPK_UPPER_DATAFLOW && (m.l1 & kMetaDfBwd)) levels_dataflow<true, CPK_DF_CH(true), true, RMAX / kWave>(S, nr, R, neb, tid);
         else if (CPK_UPPER_GROUP(true)) levels_grouped<CPK_UPPER_CH(true), true, true>(S, nl, false, tid);
         else sweep_levels<kWave, true, true, CPK_UPPER_CH(true), true, true>(S, nl, false, tid);
@@ -2471,7 +2989,7 @@ __global__ __launch_bounds__(TPB) void sptrsv_last_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip(run, active)) return;
     last_block<TPB, RPU, EPU, ADD>(smem, meta[blk0 + blockIdx.x], lvl_row, fptr, fcol, fval, bptr, bcol, bval, D, perm,
-                                   xin, neg_from, sched_in, xs, w, out, ys, uf, img);
+                                   xin, neg_from, sched_in, xs, w, out, ys, uf, blk0 + blockIdx.x, img);
 }
 
 // the last round fused (fwd + bwd) when it is an upper round whose blocks fit sptrsv_last_kernel
@@ -2630,7 +3148,7 @@ __global__ __launch_bounds__(TPB) void sptrsv_chain_kernel(
                                                        nullptr, sched_in, nullptr, xs, pk, uf, b, img, wait);
     else if (kind == 1)
         last_block<TPB, RPU, EPU, ADD, true>(smem, meta[b], lvl_row, fptr, fcol, fval, bptr, bcol, bval, D, perm, xin,
-                                             neg_from, sched_in, xs, w, out, ys, uf, img, wait);
+                                             neg_from, sched_in, xs, w, out, ys, uf, b, img, wait);
     else
         upper_block<TPB, RPU, EPU, true, ADD, true>(smem, meta[b], lvl_row, bptr, bcol, bval, D, perm, nullptr, 0, w, out,
                                                     0, ys, nullptr, pk, uf, b, img, wait);

@@ -60,6 +60,8 @@ const BoolOpt kBool[] = {
     {"all_dataflow", &EngineOpts::all_dataflow},
     {"no_colsweep", &EngineOpts::no_colsweep},
     {"all_colsweep", &EngineOpts::all_colsweep},
+    {"no_rowspan", &EngineOpts::no_rowspan},
+    {"all_rowspan", &EngineOpts::all_rowspan},
     {"no_sched_resid", &EngineOpts::no_sched_resid},
     {"no_fused_resid", &EngineOpts::no_fused_resid},
     {"tsolve_global", &EngineOpts::tsolve_global},

@@ -101,6 +101,7 @@ Precond *precond_create(Ctx &c, Analysis &&an, PrecondPre *pre) {
     pc->dF.chain_wide = c.opts.chain_wide;
     pc->dF.dataflow = c.opts.no_dataflow ? 1 : (c.opts.all_dataflow ? 2 : 0);
     pc->dF.colsweep = c.opts.no_colsweep ? 1 : (c.opts.all_colsweep ? 2 : 0);
+    pc->dF.rowspan = c.opts.no_rowspan ? 1 : (c.opts.all_rowspan ? 2 : 0);
     pc->dF.no_fused_resid = c.opts.no_fused_resid;
     pc->dF.fuse_last = !c.opts.no_fuse_last;  // single GPU: no entries outside the factor
     pc->no_sched = c.opts.no_sched_resid;
@@ -272,6 +273,7 @@ Precond *precond_create_dist(Ctx &c, Analysis &&an, const HCsr *Akry) {
     pc->dF.chain_wide = c.opts.chain_wide;
     pc->dF.dataflow = c.opts.no_dataflow ? 1 : (c.opts.all_dataflow ? 2 : 0);
     pc->dF.colsweep = c.opts.no_colsweep ? 1 : (c.opts.all_colsweep ? 2 : 0);
+    pc->dF.rowspan = c.opts.no_rowspan ? 1 : (c.opts.all_rowspan ? 2 : 0);
     pc->dF.no_fused_resid = c.opts.no_fused_resid;
     {
         Factor Fl = relabel(rp.Fsub, S);

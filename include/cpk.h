@@ -141,7 +141,10 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * s * d < delta is replaced by s * delta, see cpk_pc_factor_report; the one option besides
  * exact_dots that changes results; read at every cpk_pc_create[_hint], cpk_pc_refactor and
  * cpk_analyze), host_factor,
- * no_pipe, no_upper, no_col16, no_dataflow, all_dataflow, no_colsweep, all_colsweep, no_chain, chain_wide
+ * no_pipe, no_upper, no_col16, no_dataflow, all_dataflow, no_colsweep, all_colsweep, no_rowspan, all_rowspan
+ * (the upper rounds' row-span level loop: never / on every eligible block instead of where the host
+ * model picks it; all_rowspan goes before all_dataflow and all_colsweep, which otherwise keep
+ * their loop on every block they force), no_chain, chain_wide
  * (rounds of at most this many blocks join the sweep chain, default 256), exact_dots, no_bcast_analysis
  * (every rank of a distributed preconditioner runs the global analysis instead of receiving rank 0's),
  * apply_multi_panel (cpk_pc_apply_multi always on its panel kernels; set before building operators),
@@ -367,6 +370,25 @@ int cpk_analysis_schedule(cpk_analysis an, int64_t *nlevels, int64_t *round_ptr,
  * tsend, tdof, and {kp,ac,ab}_{ptr,col,val,send} for Kp, blkdiag(A,C) and [A B']. */
 typedef struct cpk_plan_s *cpk_plan;
 int cpk_analysis_plan(cpk_analysis an, cpk_mat A, cpk_mat C, int nranks, int rank, cpk_plan *out);
+/* Host-only: the row-span layout (the upper rounds' fourth level loop) of
+ * schedule block `block` and direction `dir` (0 forward, 1 backward), so it can be replayed
+ * without a GPU.  The layout routine is the device's; the rows' entry order is restated here
+ * (single-GPU factor, no entries outside it) and each call scans the factor: for test sizes.  cap_entries: the staged image's entry capacity (<= 0:
+ * the schedule's).  info->eligible = 0: the loop refuses the block (more than 128 rows, the rows'
+ * in-block terms not at increasing steps before their own, a run over 255 terms, over capacity);
+ * the rows and steps are exported all the same.  Any array pointer may be NULL.  The block's rows
+ * r0 .. r0 + nr - 1 (relabelled factor): rowptr[nr + 1] into col / val / dest[ne] in the device's
+ * entry order (col: relabelled row indices); step[nr] the row's step; lead[nr] its first lead
+ * slot; by step: mask[2 nr] (bit t of the pair: an in-block term at step t), base, first, run0[nr];
+ * tab[ndr * nrp]: the run length of the row of step s behind its term of the d-th drain step at
+ * tab[d * nrp + s]; info->dset: the drain steps. */
+typedef struct {
+    int64_t eligible, r0, nr, ne, slots, ndr, nrp, trips;
+    uint64_t dset[2];
+} cpk_rowspan_info;
+int cpk_analysis_rowspan(cpk_analysis an, int64_t block, int dir, int64_t cap_entries, cpk_rowspan_info *info,
+                         int64_t *rowptr, int32_t *col, double *val, int32_t *dest, int32_t *step, int32_t *lead,
+                         uint64_t *mask, int32_t *base, int32_t *first, int32_t *run0, uint8_t *tab);
 int cpk_plan_array(cpk_plan plan, const char *name, int64_t *count, void *out);
 int cpk_plan_destroy(cpk_plan plan);
 
@@ -485,10 +507,13 @@ int cpk_debug_pipe_stamps(uint64_t *out, int npairs, int *copied);
  * out[v * 131072 + block] for v = forward, forward with the fused refinement residual, backward,
  * backward accumulating; *copied = 0 unless built with -DCPK_PIPE_STAMPS (tools/blk_cycles.py). */
 int cpk_debug_blk_cycles(uint64_t *out, int64_t n, int64_t *copied);
-/* Diagnostic: the upper-round loop-cost model of a preconditioner's sweeps, 8 int64 per (upper
+/* Diagnostic: the upper-round loop-cost model of a preconditioner's sweeps, 10 int64 per (upper
  * block, direction): block, direction (0 forward), rows, level-loop trips, dataflow trips (-1:
  * not modelled), outside terms behind in-block ones, column sweep valid, loop chosen (0 level,
- * 1 dataflow, 2 column sweep).  out = NULL: *copied = the total count. */
+ * 1 dataflow, 2 column sweep, 3 column sweep with drains, 4 row-span), row-span eligible (-1: the
+ * loop is off), its drain trips (-1: not eligible).  A distributed preconditioner whose separator
+ * is solved by the block sweeps appends that sweep's records, with directions 2 (forward) and 3.
+ * out = NULL: *copied = the total count. */
 int cpk_debug_block_model(cpk_pc M, int64_t *out, int64_t n, int64_t *copied);
 /* Diagnostic: the last cpdqgmres solve of this context run with engine option profile_passes
  * (eager batches, HIP events between its passes): out[8] = {iterations, Krylov SpMV ms, M*z ms,

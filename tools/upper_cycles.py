@@ -63,10 +63,10 @@ if os.environ.get("BLOCKS"):
     _lib.check(_lib.lib.cpk_debug_block_model(M.h, None, 1 << 40, C.byref(n)))
     mod = np.zeros(max(n.value, 1), np.int64)
     _lib.check(_lib.lib.cpk_debug_block_model(M.h, mod.ctypes.data_as(C.POINTER(C.c_int64)), n.value, C.byref(n)))
-    mod = mod[:n.value].reshape(-1, 8)
+    mod = mod[:n.value].reshape(-1, 10)
     with open(os.environ["BLOCKS"], "w") as f:
-        for b, d, nr, lt, dt, outs, valid, choice in mod.tolist():
+        for b, d, nr, lt, dt, outs, valid, choice, rs_ok, rs_trips in mod.tolist():
             ph = cyc[4 + 4 * d: 8 + 4 * d, b].tolist() if b < KMAX else [0, 0, 0, 0]
             f.write(json.dumps({"b": b, "dir": d, "nr": nr, "lt": lt, "dt": dt, "outs": outs, "valid": valid,
-                                "choice": choice, "cyc": ph}) + "\n")
+                                "choice": choice, "rs_ok": rs_ok, "rs_trips": rs_trips, "cyc": ph}) + "\n")
 
