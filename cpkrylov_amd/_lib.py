@@ -124,6 +124,20 @@ _SIGS = {
     "cpk_reg_solve": ([vp, C.c_int, P(C.c_double), vp, vp, vp, vp, P(Opts), P(C.c_double), P(Stats), P(vp)],
                       C.c_int),
     "cpk_reg_solve_device": ([vp, C.c_int, vp, vp, vp, vp, vp, P(Opts), vp, P(Stats)], C.c_int),
+    "cpk_kkt_create": ([vp, vp, vp, vp, P(vp)], C.c_int),
+    "cpk_kkt_destroy": ([vp], C.c_int),
+    "cpk_kkt_get_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_kkt_set_route": ([vp, C.c_int], C.c_int),
+    "cpk_kkt_route_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_kkt_apply": ([vp, P(C.c_double), P(C.c_double)], C.c_int),
+    "cpk_kkt_apply_device": ([vp, vp, vp], C.c_int),
+    "cpk_kkt_residual": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64,
+                          P(C.c_double)], C.c_int),
+    "cpk_kkt_residual_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp], C.c_int),
+    "cpk_kkt_residual_device_sums": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, P(C.c_double)], C.c_int),
+    "cpk_kkt_solve": ([vp, C.c_int, P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int, P(Stats), P(C.c_double)],
+                      C.c_int),
+    "cpk_kkt_solve_device": ([vp, C.c_int, vp, vp, P(Opts), vp, C.c_int, P(Stats), P(C.c_double)], C.c_int),
     "cpk_method_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, vp, vp, P(Opts), P(C.c_double),
                                 C.c_int64, P(C.c_double), C.c_int64, P(Stats), P(C.c_int)], C.c_int),
     "cpk_method_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, P(Opts), vp, C.c_int64,

@@ -881,6 +881,205 @@ def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None, raise_on_error=Tru
     return x, stats, flag
 
 
+def _is_device(v):
+    """A device tensor, duck-typed as Matrix.set_values does (no tensor library is imported)."""
+    return all(hasattr(v, a) for a in ("is_cuda", "data_ptr", "dtype", "is_contiguous")) and bool(v.is_cuda)
+
+
+def _device_operand(v, what, rows):
+    """(address, columns, leading dimension) of a contiguous float64 device tensor holding `rows`
+    values, or k columns of `rows` values each, one column after the other (a (k, rows) row-major
+    tensor is the N x k column-major block); its stream is synchronised first."""
+    if "float64" not in str(v.dtype) or not v.is_contiguous():
+        raise CpkError(_lib.CPK_ERR_ARGS, f"{what}: a contiguous float64 device tensor expected")
+    count = int(v.numel())
+    if rows == 0 or count % rows:
+        if count != rows:
+            raise CpkError(_lib.CPK_ERR_DIM, f"{what}: a multiple of N = {rows} values expected")
+    mod = sys.modules[type(v).__module__.split(".")[0]]  # the tensor's own library, already loaded
+    mod.cuda.current_stream(v.device).synchronize()
+    return C.c_void_p(v.data_ptr() or None), (count // rows if rows else 1), max(rows, 1)
+
+
+def _norms_dict(nr, vector):
+    q = np.asarray(nr, dtype=np.float64).reshape(-1, 4)
+    d = {"rr_x": q[:, 0].copy(), "rr_y": q[:, 1].copy(), "bb_x": q[:, 2].copy(), "bb_y": q[:, 3].copy()}
+    d["rnorm"] = np.sqrt(d["rr_x"] + d["rr_y"])
+    d["bnorm"] = np.sqrt(d["bb_x"] + d["bb_y"])
+    return {k: float(v[0]) for k, v in d.items()} if vector else d
+
+
+class KKT:
+    """The saddle-point operator K = [A B'; B -C] of the system reg_cpkrylov solves (A, B, C as
+    the solvers take them: C is the positive block; A may be nonsymmetric), resident on the GPU.
+
+    K follows its matrices: after `Matrix.set_values` (host or device values) the next use
+    regathers K's values on the device.  A, B, C may be `Matrix` handles (shared with the solvers
+    and the preconditioner) or scipy / dense matrices; K keeps them alive.
+
+    Operands are NumPy arrays (a vector, or an N x k array for a block) or device tensors (anything
+    with is_cuda, data_ptr(), dtype, is_contiguous(): float64, contiguous, one column of N values
+    after the other, so a (k, N) row-major tensor is the N x k block).  With device operands the
+    result goes to the device tensor passed as `out=` and nothing crosses PCIe but the sums."""
+
+    def __init__(self, A, B, Cm, ctx=None):
+        first = next((M for M in (A, B, Cm) if isinstance(M, Matrix)), None)
+        self.ctx = ctx or (first.ctx if first is not None else None) or default_context()
+        self.A, self.B, self.C = (_as_matrix(M, self.ctx) for M in (A, B, Cm))
+        h = C.c_void_p()
+        check(lib.cpk_kkt_create(self.ctx.h, self.A.h, self.B.h, self.C.h, C.byref(h)))
+        self.h = h
+        self.n, self.m = self.A.shape[0], self.C.shape[0]
+        self.N = self.n + self.m
+        self.shape = (self.N, self.N)
+
+    def info(self):
+        """Diagnostic (cpk_kkt_get_info): sizes, the values generations of A, B, C that K holds, the
+        device regather passes so far and the device address of K's value array (it never moves)."""
+        v = (C.c_int64 * 8)()
+        check(lib.cpk_kkt_get_info(self.h, v))
+        return {"n": v[0], "m": v[1], "nnz": v[2], "values_generations": (v[3], v[4], v[5]), "refreshes": v[6],
+                "values_address": v[7]}
+
+    def set_route(self, route):
+        """Routing of the block residual: "auto" (panels of 8 columns from the measured crossover,
+        a loop of single-column passes below it), "panel" or "loop" (forced; the same bits)."""
+        check(lib.cpk_kkt_set_route(self.h, {"auto": 0, "panel": 1, "loop": 2}[route]))
+
+    def route_info(self):
+        v = (C.c_int64 * 4)()
+        check(lib.cpk_kkt_route_info(self.h, v))
+        return {"panel_columns": v[0], "crossover": v[1], "route": ("auto", "panel", "loop")[v[2]], "panels": v[3]}
+
+    def _host_block(self, a, what):
+        a = np.asarray(a, dtype=np.float64)
+        vector = a.ndim == 1
+        if a.ndim not in (1, 2) or a.shape[0] != self.N:
+            raise CpkError(_lib.CPK_ERR_DIM, f"{what} must have N = {self.N} rows")
+        return np.asfortranarray(a.reshape(self.N, -1)), vector
+
+    def __matmul__(self, z):
+        return self.apply(z)
+
+    def apply(self, z, out=None):
+        """y = K @ z: a vector or an N x k array; device tensors with out=.  A host block is a
+        convenience: one staged cpk_kkt_apply per column (device tensors avoid the staging)."""
+        if _is_device(z):
+            if out is None or not _is_device(out):
+                raise CpkError(_lib.CPK_ERR_ARGS, "K @ z on device operands: pass the result tensor as out=")
+            zp, k, ld = _device_operand(z, "z", self.N)
+            op, ko, _ = _device_operand(out, "out", self.N)
+            if ko != k:
+                raise CpkError(_lib.CPK_ERR_DIM, "out must have z's shape")
+            for j in range(k):
+                off = 8 * j * ld
+                check(lib.cpk_kkt_apply_device(self.h, C.c_void_p((zp.value or 0) + off), C.c_void_p((op.value or 0) + off)))
+            check(lib.cpk_ctx_synchronize(self.ctx.h))
+            return out
+        Z, vector = self._host_block(z, "z")
+        Y = np.zeros_like(Z, order="F")
+        for j in range(Z.shape[1]):
+            zj, yj = np.ascontiguousarray(Z[:, j]), np.zeros(self.N)
+            check(lib.cpk_kkt_apply(self.h, _dptr(zj), _dptr(yj)))
+            Y[:, j] = yj
+        return Y[:, 0].copy() if vector else Y
+
+    def residual(self, z, b, out=None, want_r=True):
+        """r = b - K @ z and the sums of squares of r and b, split at row n: returns (r, norms) with
+        norms = {rr_x, rr_y, bb_x, bb_y, rnorm, bnorm} (floats for a vector, arrays of k for a
+        block).  rr_* and bb_* are the device's sums (exact under engine option exact_dots), rnorm
+        and bnorm their roots.  Device operands: r goes to out= (which may be b itself); with
+        want_r=False no r is stored and None is returned for it."""
+        if _is_device(z) or _is_device(b):
+            if not (_is_device(z) and _is_device(b)):
+                raise CpkError(_lib.CPK_ERR_ARGS, "residual: z and b must both be host arrays or both device tensors")
+            zp, k, ld = _device_operand(z, "z", self.N)
+            bp, kb, _ = _device_operand(b, "b", self.N)
+            if kb != k:
+                raise CpkError(_lib.CPK_ERR_DIM, "b must have z's shape")
+            rp = C.c_void_p(None)
+            if want_r:
+                if out is None or not _is_device(out):
+                    raise CpkError(_lib.CPK_ERR_ARGS, "residual on device operands: pass the result tensor as out=")
+                rp, kr, _ = _device_operand(out, "out", self.N)
+                if kr != k:
+                    raise CpkError(_lib.CPK_ERR_DIM, "out must have z's shape")
+            nr = np.zeros(4 * max(k, 1))  # host memory: the entry copies the sums back and waits
+            check(lib.cpk_kkt_residual_device_sums(self.h, k, zp, ld, bp, ld, rp, ld, _dptr(nr)))
+            return (out if want_r else None), _norms_dict(nr[:4 * k], getattr(z, "ndim", 2) == 1)
+        Z, vector = self._host_block(z, "z")
+        Bm, _ = self._host_block(b, "b")
+        if Bm.shape != Z.shape:
+            raise CpkError(_lib.CPK_ERR_DIM, "b must have z's shape")
+        k, ld = Z.shape[1], max(self.N, 1)
+        R = np.zeros_like(Z, order="F") if want_r else None
+        nr = np.zeros(4 * max(k, 1))
+        check(lib.cpk_kkt_residual(self.h, k, _dptr(Z), ld, _dptr(Bm), ld, _dptr(R) if want_r else None, ld, _dptr(nr)))
+        r = None if not want_r else (R[:, 0].copy() if vector else R)
+        return r, _norms_dict(nr[:4 * k], vector)
+
+    def solve(self, method, b, M, opts=None, x0=None, out=None):
+        """x, stats, flag = K.solve(method, b, M, opts, x0): reg_cpkrylov's driver with the existing
+        preconditioner M (an opLDL2 built on K's matrices), checked against K itself.
+
+        x0 is None: the cold solve, cpk_reg_solve_device on K's handles unchanged.  With x0 the
+        call forms r = b - K @ x0 on the device, runs the same driver on r and returns x0 + dx: THE
+        STOP TEST THEN RUNS ON THE CORRECTION SYSTEM (atol, rtol relative to r's initial
+        preconditioned residual, not b's).  stats["true_resid0"] and stats["true_resid"] hold the
+        sums and norms (as `residual` returns them) of the start residual (cold: of b) and of
+        b - K @ x for the returned x.  Device operands: b a device tensor and the result in out=; a
+        warm start passes x0=out, which holds x0 on entry and is updated in place.  A stop inside
+        the driver raises its own error, carrying `partial` = (x0 plus whatever the driver wrote,
+        the eight sums)."""
+        name = getattr(method, "_cpk_method", method)
+        if name not in _lib.METHODS:
+            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+        if not isinstance(M, opLDL2):
+            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
+        res = np.zeros(8)
+        if _is_device(b):
+            if out is None or not _is_device(out):
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve on device operands: pass the result tensor as out=")
+            if x0 is not None and x0 is not out:
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve on device operands: x0 is out itself (x0 is updated in place)")
+            bp, kb, _ = _device_operand(b, "b", self.N)
+            xp, kx, _ = _device_operand(out, "out", self.N)
+            if kb != 1 or kx != 1:
+                raise CpkError(_lib.CPK_ERR_DIM, "solve takes one right-hand side of N entries")
+            rc = lib.cpk_kkt_solve_device(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp,
+                                          int(x0 is not None), C.byref(st), _dptr(res))
+            x = out
+        else:
+            b = np.ascontiguousarray(np.asarray(b, dtype=np.float64)).ravel()
+            if b.shape[0] != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
+            if x0 is None:
+                x = np.zeros(self.N)
+            else:
+                x = np.array(x0, dtype=np.float64).ravel()
+                if x.shape[0] != self.N:
+                    raise CpkError(_lib.CPK_ERR_DIM, "x0 must have n+m entries")
+            rc = lib.cpk_kkt_solve(self.h, _lib.METHODS[name], _dptr(b), M.h, C.byref(make_opts(opts)), _dptr(x),
+                                   int(x0 is not None), C.byref(st), _dptr(res))
+        if rc != _lib.CPK_OK:
+            try:
+                check(rc)
+            except CpkError as e:
+                e.partial = (x, res.copy())  # x0 plus whatever the driver wrote, and the sums
+                raise
+        stats, flag = _stats_from(name, st, hist, lq, qr)
+        stats["ptime"], stats["stime"] = st.ptime, st.stime
+        stats["true_resid0"] = _norms_dict(res[:4], True)
+        stats["true_resid"] = _norms_dict(res[4:], True)
+        return x, stats, flag
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib.cpk_kkt_destroy(self.h)
+            self.h = None
+
+
 def SymGivens(a, b):
     """[c, s, d] = SymGivens(a, b)  (util/SymGivens.m)."""
     c, s, d = C.c_double(), C.c_double(), C.c_double()

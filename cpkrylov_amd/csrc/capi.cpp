@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <memory>
 #include <new>
@@ -142,6 +143,38 @@ struct cpk_mat_s {
             if (op.vc != C->vgen) refresh_half(ctx->c, C, m.val.p + h.nnz()), op.vc = C->vgen;
         }
         return *op.m;
+    }
+};
+
+// K = [A B'; B -C] on the device in assemble_kp's entry order, with the handles' generations it
+// holds and the map from their stored values (kp_value_sources' order) to its value array
+struct cpk_kkt_s {
+    cpk_ctx_s *ctx = nullptr;
+    cpk_mat_s *A = nullptr, *B = nullptr, *C = nullptr;  // must outlive K
+    uint64_t gen[3] = {0, 0, 0}, vgen[3] = {0, 0, 0};
+    int64_t n = 0, m = 0, refreshes = 0;
+    DMat K;
+    DBuf<uint32_t> src;  // entry q <- entry src[q] of [A's values; B's values; C's values]
+    DBuf<double> norms;  // the device side of a call's sums (8: cpk_kkt_solve's res)
+    // the block residual's routing (0: by kKktPanelMinCols, 1: always the panel, 2: always the loop),
+    // the panels run so far, and the panel path's work array (N * kMultiKP), allocated on first use
+    int route = 0;
+    int64_t panels = 0;
+    DBuf<double> Tp;
+    // the operator on the handles' current values: a device gather where a values generation
+    // moved (the value array keeps its address; nothing goes through the host)
+    const DMat &current() {
+        if (A->gen != gen[0] || B->gen != gen[1] || C->gen != gen[2])
+            throw Error(CPK_ERR_ARGS, "kkt: a matrix handle of K was destroyed or replaced");
+        if (A->vgen != vgen[0] || B->vgen != vgen[1] || C->vgen != vgen[2]) {
+            const DMat &a = A->dev(), &b = B->dev(), &c = C->dev();
+            if (a.nnz + 2 * b.nnz + c.nnz != K.nnz || (int64_t)src.n != K.nnz)
+                throw Error(CPK_ERR_ARGS, "kkt: the value map does not match the handles");
+            launch_kkt_gather(ctx->c, src.p, K.nnz, a.val.p, a.nnz, b.val.p, b.nnz, c.val.p, K.val.p);
+            vgen[0] = A->vgen, vgen[1] = B->vgen, vgen[2] = C->vgen;
+            refreshes++;
+        }
+        return K;
     }
 };
 
@@ -865,6 +898,258 @@ int cpk_reg_shift_device(cpk_ctx ctx, const double *d_b, cpk_mat A, cpk_mat B, c
     const ShiftOps so = shift_ops(A, C, *M->p);
     int s = reg_shift_device(ctx->c, d_b, *so.A, *so.Bt, so.bt_colmin, *M->p, d_b1, d_xy0);
     if (shifted) *shifted = s;
+    API_END
+}
+
+// ---- the saddle-point operator K = [A B'; B -C]: product, true residual, verified solve ----------
+int cpk_kkt_create(cpk_ctx ctx, cpk_mat A, cpk_mat B, cpk_mat C, cpk_kkt *out) {
+    API_BEGIN
+    need(ctx && A && B && C && out, "NULL argument");
+    need(A->ctx == ctx && B->ctx == ctx && C->ctx == ctx, "kkt: the matrices belong to another context");
+    check_kp_dims(A->h, B->h, C->h);
+    if (ctx->c.dist())
+        throw Error(CPK_ERR_UNSUPPORTED, "kkt: single-GPU only (a distributed context keeps row slices, not K)");
+    auto k = std::make_unique<cpk_kkt_s>();
+    k->ctx = ctx, k->A = A, k->B = B, k->C = C;
+    k->n = A->h.nrows, k->m = C->h.nrows;
+    HCsr negC = C->host();
+    for (auto &v : negC.val) v = -v;
+    const HCsr &ha = A->host(), &hb = B->host();
+    make_dmat(assemble_kp(ha, hb, negC), k->K);
+    const std::vector<int64_t> ks = kp_value_sources(ha, hb, negC);
+    const int64_t off[3] = {0, ha.nnz(), ha.nnz() + hb.nnz()};
+    std::vector<uint32_t> src(ks.size());
+    for (size_t q = 0; q < ks.size(); q++) src[q] = (uint32_t)(off[ks[q] >> 40] + (ks[q] & ((int64_t(1) << 40) - 1)));
+    k->src.upload(src);
+    k->norms.alloc(8);
+    const cpk_mat_s *h[3] = {A, B, C};
+    for (int i = 0; i < 3; i++) k->gen[i] = h[i]->gen, k->vgen[i] = h[i]->vgen;
+    *out = k.release();
+    API_END
+}
+
+int cpk_kkt_destroy(cpk_kkt K) {
+    API_BEGIN
+    delete K;  // hipFree waits for the device; the context may already be gone
+    API_END
+}
+
+int cpk_kkt_get_info(cpk_kkt K, int64_t info[8]) {
+    API_BEGIN
+    need(K && info, "NULL argument");
+    const int64_t v[8] = {K->n, K->m, K->K.nnz, (int64_t)K->vgen[0], (int64_t)K->vgen[1], (int64_t)K->vgen[2],
+                          K->refreshes, (int64_t)(uintptr_t)K->K.val.p};
+    std::memcpy(info, v, sizeof v);
+    API_END
+}
+
+int cpk_kkt_apply_device(cpk_kkt K, const double *d_z, double *d_y) {
+    API_BEGIN
+    need(K && ((d_z && d_y) || !(K->n + K->m)), "NULL argument");
+    launch_kkt_apply(K->ctx->c, K->current(), d_z, d_y);
+    API_END
+}
+
+int cpk_kkt_apply(cpk_kkt K, const double *z, double *y) {
+    API_BEGIN
+    need(K && ((z && y) || !(K->n + K->m)), "NULL argument");
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    if (N == 0) return CPK_OK;
+    DBuf<double> dz, dy;
+    h2d(dz, z, (size_t)N);
+    dy.alloc((size_t)N);
+    launch_kkt_apply(c, K->current(), dz.p, dy.p);
+    CPK_HIP(hipMemcpyAsync(y, dy.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    API_END
+}
+
+// the checks of both residual entries; nothing is touched before they pass
+static void check_kkt_resid(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb,
+                            const double *R, int64_t ldr) {
+    need(K && Z && Bm, "NULL argument");
+    const int64_t N = K->n + K->m;
+    if (k < 0 || ldz < N || ldb < N || (R && ldr < N))
+        throw Error(CPK_ERR_DIM, "kkt_residual: k >= 0 and leading dimensions >= N required");
+}
+
+// Panels of kMultiKP columns.  A panel below the measured crossover (or with the loop forced) is a
+// loop of single-column passes.  Otherwise K is streamed once for the panel (kkt_panel_kernel: every
+// column's R in spmv_stream's row order) and each column's sums are taken from its r and b by
+// kkt_sums_kernel in the single-column pass's order -- so either path gives a column the same
+// bits, and the routing cannot change one.  r goes to a work array when the caller wants no R or
+// wants it over Bm (the sums read b after r exists), and is copied over Bm afterwards.
+static void kkt_resid_block(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_B, int64_t ldb,
+                            double *d_R, int64_t ldr, double *d_norms) {
+    const DMat &Kd = K->current();
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    if (!d_R && !d_norms) return;
+    for (int64_t j0 = 0; j0 < k; j0 += kMultiKP) {
+        const int kc = (int)std::min<int64_t>(kMultiKP, k - j0);
+        const bool panel = N > 0 && (K->route == 1 || (K->route == 0 && kc >= kKktPanelMinCols));
+        if (!panel) {
+            for (int64_t j = j0; j < j0 + kc; j++)
+                launch_kkt_resid(c, Kd, K->n, d_Z + j * ldz, d_B + j * ldb, d_R ? d_R + j * ldr : nullptr,
+                                 d_norms ? d_norms + 4 * j : nullptr);
+            continue;
+        }
+        const size_t pn = (size_t)N * kMultiKP;
+        const bool aside = !d_R || d_R == d_B;
+        if (aside && K->Tp.n < pn) K->Tp.alloc(pn);
+        double *dst = aside ? K->Tp.p : d_R + j0 * ldr;
+        const int64_t ldd = aside ? N : ldr;
+        launch_kkt_panel(c, Kd, kc, d_Z + j0 * ldz, ldz, d_B + j0 * ldb, ldb, dst, ldd);
+        if (d_norms)
+            for (int j = 0; j < kc; j++)
+                launch_kkt_sums(c, Kd, K->n, dst + j * ldd, d_B + (j0 + j) * ldb, d_norms + 4 * (j0 + j));
+        if (d_R && aside)
+            CPK_HIP(hipMemcpy2DAsync(d_R + j0 * ldr, (size_t)ldr * sizeof(double), dst, (size_t)ldd * sizeof(double),
+                                     (size_t)N * sizeof(double), (size_t)kc, hipMemcpyDeviceToDevice, c.stream));
+        K->panels++;
+    }
+}
+
+int cpk_kkt_set_route(cpk_kkt K, int route) {
+    API_BEGIN
+    need(K != nullptr, "NULL argument");
+    need(route >= 0 && route <= 2, "kkt_set_route: 0 (by the crossover), 1 (panel) or 2 (loop)");
+    K->route = route;
+    API_END
+}
+
+int cpk_kkt_route_info(cpk_kkt K, int64_t info[4]) {
+    API_BEGIN
+    need(K && info, "NULL argument");
+    const int64_t v[4] = {kMultiKP, kKktPanelMinCols, K->route, K->panels};
+    std::memcpy(info, v, sizeof v);
+    API_END
+}
+
+int cpk_kkt_residual_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                            double *d_R, int64_t ldr, double *d_norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
+    if (k == 0) return CPK_OK;
+    kkt_resid_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
+    API_END
+}
+
+// device operands, the sums to HOST memory: they are taken in a device buffer, copied back and
+// waited for, so a caller without a device allocator (the Python class) can have them
+int cpk_kkt_residual_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                                 double *d_R, int64_t ldr, double *norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
+    need(norms != nullptr, "NULL argument");
+    if (k == 0) return CPK_OK;
+    Ctx &c = K->ctx->c;
+    DBuf<double> dn;
+    dn.alloc(4 * (size_t)k);
+    kkt_resid_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, dn.p);
+    CPK_HIP(hipMemcpyAsync(norms, dn.p, dn.bytes(), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    API_END
+}
+
+int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
+                     int64_t ldr, double *norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, Z, ldz, Bm, ldb, R, ldr);
+    if (k == 0) return CPK_OK;
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    HostBlock dZ(N, k), dB(N, k);
+    DBuf<double> dn;
+    if (norms) dn.alloc(4 * (size_t)k);
+    dZ.up(Z, ldz), dB.up(Bm, ldb);
+    // in place on the staged right-hand sides: a row reads b_i before it writes r_i
+    kkt_resid_block(K, k, dZ.d.p, dZ.ld(), dB.d.p, dB.ld(), R ? dB.d.p : nullptr, dB.ld(), dn.p);
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (R) dB.down(R, ldr);
+    if (norms) CPK_HIP(hipMemcpy(norms, dn.p, 4 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
+// cold: reg_cpkrylov's driver on b (cpk_reg_solve_device's call exactly).  warm: r = b - K*x0, the
+// same driver on r (its shift included, reg_cpkrylov.m:152-175), x = x0 + dx.  res (host, 8):
+// the four sums of the start residual, then those of b - K*x for the returned x.
+static void kkt_solve_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
+                           cpk_stats *stats, double *res) {
+    cpk_mat A = K->A, C = K->C;
+    need(M->ctx == K->ctx, "kkt_solve: M belongs to another context");
+    check_method_dims(A, C, M);
+    Ctx &c = K->ctx->c;
+    Precond &p = *M->p;
+    const int64_t N = K->n + K->m;
+    const DMat &Kd = K->current();
+    const DMat &AC = A->krylov_op(C, p);
+    const ShiftOps so = shift_ops(A, C, p);
+    double *dn = K->norms.p;
+    if (stats) stats->ptime = p.ptime;  // also where the driver stops with its error
+    auto finish = [&] {
+        launch_kkt_resid(c, Kd, K->n, d_x, d_b, nullptr, dn + 4);
+        if (res) CPK_HIP(hipMemcpyAsync(res, dn, 8 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+    };
+    if (!warm) {
+        // the start residual of x = 0 is b: its sums in the residual pass's order, K not streamed
+        if (N) CPK_HIP(hipMemsetAsync(d_x, 0, N * sizeof(double), c.stream));
+        launch_kkt_sums(c, Kd, K->n, d_b, d_b, dn);
+        try {
+            reg_solve_device(c, method, d_b, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_x, stats);
+        } catch (...) {
+            finish();
+            throw;
+        }
+    } else {
+        DBuf<double> r, dx;
+        r.alloc((size_t)std::max<int64_t>(N, 1)), dx.alloc((size_t)std::max<int64_t>(N, 1));
+        dx.zero(c.stream);
+        launch_kkt_resid(c, Kd, K->n, d_x, d_b, r.p, dn);
+        std::exception_ptr err;
+        try {
+            reg_solve_device(c, method, r.p, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dx.p, stats);
+        } catch (...) {
+            err = std::current_exception();
+        }
+        launch_recover(c, N, d_x, dx.p, d_x);  // x0 plus whatever the driver wrote
+        if (err) {
+            finish();
+            std::rethrow_exception(err);
+        }
+    }
+    finish();
+}
+
+int cpk_kkt_solve_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
+                         cpk_stats *stats, double *res) {
+    API_BEGIN
+    need(K && M && ((d_b && d_x) || !(K->n + K->m)), "NULL argument");
+    kkt_solve_core(K, method, d_b, M, opts, d_x, warm, stats, res);
+    API_END
+}
+
+int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_opts *opts, double *x, int warm,
+                  cpk_stats *stats, double *res) {
+    API_BEGIN
+    need(K && M && ((b && x) || !(K->n + K->m)), "NULL argument");
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    DBuf<double> db, dx;
+    h2d(db, b, (size_t)N);
+    if (warm) h2d(dx, x, (size_t)N);
+    else dx.alloc((size_t)std::max<int64_t>(N, 1));
+    std::exception_ptr err;
+    try {
+        kkt_solve_core(K, method, db.p, M, opts, dx.p, warm, stats, res);
+    } catch (...) {
+        err = std::current_exception();
+    }
+    if (N) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (err) std::rethrow_exception(err);
     API_END
 }
 

@@ -232,6 +232,23 @@ void upload_value_map(const ValueMap &vm, DValueMap &dm);
 // out (nnz stored entries) from the creating call's value order `in`, both on the device, on the
 // context stream (setvalues.hip); nothing is waited for
 void launch_set_values(Ctx &c, const ValueMap &vm, const DValueMap &dm, int64_t nnz, const double *in, double *out);
+// The saddle-point operator K = [A B'; B -C] (kkt.hip; K in assemble_kp's entry order, n = size of
+// the (1,1) block), all on the context stream, nothing waited for:
+// out[q] = the entry src[q] of [va (na); vb (nb); vc], the vc entries negated
+void launch_kkt_gather(Ctx &c, const uint32_t *src, int64_t nnz, const double *va, int64_t na, const double *vb,
+                       int64_t nb, const double *vc, double *out);
+// y = K*z
+void launch_kkt_apply(Ctx &c, const DMat &K, const double *z, double *y);
+// r = b - K*z (r null: not stored; r == b allowed) and, norms not null, norms[0..3] = sum r(1:n)^2,
+// sum r(n+1:N)^2, sum b(1:n)^2, sum b(n+1:N)^2 (device memory; the exact sums under exact_dots)
+void launch_kkt_resid(Ctx &c, const DMat &K, int64_t n, const double *z, const double *b, double *r, double *norms);
+// norms[0..3] of a column whose r is in memory, bit-equal to launch_kkt_resid's sums of the same r
+// and b in both modes (the same grid, rows per thread and finish)
+void launch_kkt_sums(Ctx &c, const DMat &K, int64_t n, const double *r, const double *b, double *norms);
+// R(:, j) = B(:, j) - K*Z(:, j) for a panel of kc <= 8 columns, column-major with leading dimensions,
+// K streamed once; every column bit-equal to launch_kkt_resid's r (R == B allowed)
+void launch_kkt_panel(Ctx &c, const DMat &K, int kc, const double *Z, int64_t ldz, const double *B, int64_t ldb, double *R,
+                      int64_t ldr);
 struct DistCsr;
 void make_dist_dmat(const DistCsr &a, int nranks, DMat &d);
 // allgather the halo of x (local vector) into A.rbuf
@@ -259,6 +276,14 @@ constexpr int kMultiKP = 8;  // columns per panel
 // DESIGN.md "Refined block apply": at S10 +-4 a panel of 6 columns still loses to six
 // single-column applies, 9.70 against 9.03 ms, a panel of 7 wins, 9.79 against 10.53 ms)
 constexpr int kApplyMultiMinCols = 7;
+// the block residual of the saddle-point operator (cpk_kkt_residual) runs a panel of fewer columns
+// than this as a loop of single-column passes: the smallest k from which the panel path wins in
+// every round on both measured systems.  Measured on vectors not left in the last-level cache
+// (profiles/kkt_timing.json, DESIGN.md "The saddle-point operator K"): at S10 +-4 the panel wins from
+// 7 columns (1.248 against 1.324 ms for 8), at 10^6 dofs it loses at every size (0.225 against
+// 0.210 ms for 8), so no such k exists yet and the constant is above a full panel: the entry routes
+// every panel to the loop, and the panel path runs where cpk_kkt_set_route forces it
+constexpr int kKktPanelMinCols = kMultiKP + 1;
 struct MultiPlan {
     bool ready = false;
     std::vector<size_t> lds;

@@ -2137,6 +2137,11 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
     }
 }
 
+// x = x0 + dx, one rounding per entry (x may be x0): the recovery of a warm-started solve
+void launch_recover(Ctx &c, int64_t N, const double *d_x0, const double *d_dx, double *d_x) {
+    launch_ew(c, N, Recover{d_x0, d_dx, d_x});
+}
+
 int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
                      double *d_b1, double *d_xy0) {
     const int64_t n = M.n, m = M.m, N = M.N;

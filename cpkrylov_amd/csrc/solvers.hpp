@@ -13,6 +13,8 @@ void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, con
                       int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
 int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
                      double *d_b1, double *d_xy0);
+// x = x0 + dx (the Recover functor of the shift's recovery; d_x may be d_x0), on the context stream
+void launch_recover(Ctx &c, int64_t N, const double *d_x0, const double *d_dx, double *d_x);
 // The lockstep block solve: column j of XY (N x k, [x; y]) is method(b(:, j), A, C, M, opts)
 // (kernels/cpcg.m, kernels/cpminres.m), panels of kMultiKP columns sharing one Krylov product and
 // one panel apply per iteration.  stats / col_status: k entries or null.  Returns CPK_OK or the

@@ -409,6 +409,73 @@ int cpk_reg_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_mat B
 int cpk_reg_solve_device(cpk_ctx ctx, int method, const double *d_b, cpk_mat A, cpk_mat B, cpk_mat C,
                          cpk_pc M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
 
+/* ---- the saddle-point operator itself: product, true residual, verified solve ------------ */
+/* K = [A B'; B -C], the matrix of the system reg_cpkrylov solves (reg_cpkrylov.m:1-40): A, B, C
+ * are the handles the solvers take, C the positive block, so K holds -C; A may be nonsymmetric
+ * and the (1,1) block is A as given.  Row i < n is A's row followed by B''s entries by ascending
+ * constraint, row n + i is B's row followed by -C's row (opLDL2.m:81's assembly).  Dimension
+ * errors are opLDL2's (CPK_ERR_DIM, opLDL2.m:61-75, same messages); a distributed context is
+ * refused with CPK_ERR_UNSUPPORTED, as cpk_mat_set_values is.
+ * K follows the handles' values: at each use, if cpk_mat_set_values[_device] moved a handle's
+ * values generation, one device pass regathers K's value array from the handles' device values
+ * (the array keeps its address; nothing goes through the host).  THE THREE HANDLES MUST OUTLIVE K.
+ * cpk_kkt_get_info: {n, m, nnz(K), the values generations of A, B, C that K holds, the number of
+ * regather passes so far, the device address of K's value array}. */
+typedef struct cpk_kkt_s *cpk_kkt;
+int cpk_kkt_create(cpk_ctx ctx, cpk_mat A, cpk_mat B, cpk_mat C, cpk_kkt *out);
+int cpk_kkt_destroy(cpk_kkt K);
+int cpk_kkt_get_info(cpk_kkt K, int64_t info[8]);
+/* y = K*z (N = n + m entries each): y_i = s_i, where the row sum s_i starts at 0.0 and adds the
+ * separately rounded products K_ij*z_j in the assembled entry order (no FMA).  Host arrays, or
+ * device arrays enqueued on the context stream (_device; nothing is waited for). */
+int cpk_kkt_apply(cpk_kkt K, const double *z, double *y);
+int cpk_kkt_apply_device(cpk_kkt K, const double *d_z, double *d_y);
+/* The true residual of an N x k block: R(:, j) = Bm(:, j) - K*Z(:, j), r_i = b_i - s_i with the
+ * row sum above, and norms[4 j .. 4 j + 3] = sum r(1:n)^2, sum r(n+1:N)^2, sum b(1:n)^2,
+ * sum b(n+1:N)^2 of column j: sums, not roots; a fixed-order sum each, or under the engine option
+ * exact_dots the correctly rounded exact sum of its TwoProd pairs.  Column-major with ldz, ldb,
+ * ldr >= N; rows beyond N are not touched.  R or norms may be NULL; R == Bm with ldr == ldb is
+ * allowed (a row reads b_i before it writes r_i).  Column j's R and sums do not depend on k, on j
+ * or on the other columns (a NaN stays in its column), and equal the single-column call's.
+ * Refused before anything is written: NULL K, Z or Bm (CPK_ERR_ARGS); k < 0 or a leading
+ * dimension below N (CPK_ERR_DIM).  k == 0 does nothing.  _device: device arrays (d_norms too),
+ * enqueued on the context stream, nothing waited for.  _device_sums: the same device operands
+ * with the sums returned to HOST memory (4 k doubles, required): the one variant that waits for
+ * the stream, for a caller that has no device allocator; not for use during stream capture. */
+int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
+                     int64_t ldr, double *norms);
+int cpk_kkt_residual_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                            double *d_R, int64_t ldr, double *d_norms);
+int cpk_kkt_residual_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm,
+                                 int64_t ldb, double *d_R, int64_t ldr, double *norms);
+/* Routing of the block residual.  Columns go in panels of 8; a panel streams K once for its
+ * columns (one panel product, then each column's sums from its r and b in the single-column
+ * pass's order), and a panel of fewer columns than the measured crossover runs as a
+ * loop of single-column passes instead.  Either path gives a column the same bits in both modes,
+ * so the routing never changes a result.  cpk_kkt_set_route: 0 by the crossover (default), 1
+ * always the panel path, 2 always the loop (tests, measurements).  cpk_kkt_route_info:
+ * {columns per panel, the crossover, the route in force, panels run on the panel path so far}. */
+int cpk_kkt_set_route(cpk_kkt K, int route);
+int cpk_kkt_route_info(cpk_kkt K, int64_t info[4]);
+/* The verified, optionally warm-started solve of K*x = b with an existing M, one right-hand side.
+ * M must be the preconditioner of K's own B and C (opLDL2(G, B, -C)): the driver's shift uses M's
+ * copy of B', which the call cannot compare with K's; only M's context and dimensions are checked.
+ * warm == 0: cpk_reg_solve_device(ctx, method, b, A, B, C, M, opts, x, stats) on K's handles,
+ * unchanged.  warm != 0: x holds x0 on entry, and the call composes reg_cpkrylov's driver
+ * (reg_cpkrylov.m:152-175) around the residual: r = b - K*x0 (cpk_kkt_residual), the same driver
+ * on r (its shift included when r(n+1:N) is nonzero), x = x0 + dx with one rounding per entry.
+ * THE METHOD'S STOP TEST THEN RUNS ON THE CORRECTION SYSTEM: atol and rtol are relative to the
+ * initial preconditioned residual of r, not of b.  res (HOST memory in both variants, 8 doubles,
+ * may be NULL): res[0..3] the four sums (cpk_kkt_residual's order) of the start residual --
+ * warm of b - K*x0, cold of b itself (so res[0..1] == res[2..3]) -- and res[4..7] those of
+ * b - K*x for the returned x.  All six methods.  A stop inside the driver (CPK_ERR_INDEFINITE)
+ * is returned with the driver's own code and message; x is then x0 plus whatever the driver wrote
+ * (cold: what it wrote), and res is still filled.  b, x: N entries, host or (_device) device. */
+int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_opts *opts, double *x, int warm,
+                  cpk_stats *stats, double *res);
+int cpk_kkt_solve_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
+                         cpk_stats *stats, double *res);
+
 /* ---- a block of right-hand sides in lockstep (cpcg and cpminres) ------------------------ */
 /* [X(:,j), Y(:,j), stats(j), flag(j)] = method(B(:,j), A, C, M, opts) for j < k
  * (kernels/cpcg.m:1, kernels/cpminres.m:1, column by column; the reference has no block solve).

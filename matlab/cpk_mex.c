@@ -27,6 +27,20 @@
  *                                               % up to histLen(j) and zero below.  A column on which the
  *                                               % reference stops with its error does not raise: its
  *                                               % stats.status is 1 (CPK_ERR_INDEFINITE), the others 0
+ *   k = cpk_mex('kkt_create', A, B, C)          % the operator K = [A B'; B -C] of the system
+ *                                               % reg_cpkrylov solves (reg_cpkrylov.m:1-40); the
+ *                                               % handle owns device copies of A, B, C
+ *   Y = cpk_mex('kkt_apply', k, Z)              % Y = K*Z, Z dense N x c
+ *   [R, sums] = cpk_mex('kkt_residual', k, Z, B)   % R = B - K*Z, B and Z dense N x c; sums is 4 x c:
+ *                                               % sum r(1:n)^2, r(n+1:N)^2, b(1:n)^2, b(n+1:N)^2 per column
+ *   [x, stats, flag, res] = cpk_mex('kkt_solve', k, name, b, h, opts[, x0])
+ *                                               % reg_cpkrylov's shift, method and recovery
+ *                                               % (reg_cpkrylov.m:152-175) with the preconditioner h,
+ *                                               % checked against K: res(1:4) the sums of the start
+ *                                               % residual, res(5:8) those of b - K*x.  With x0 the solve
+ *                                               % starts there: r = b - K*x0, the driver on r, x = x0 + dx
+ *                                               % (atol, rtol then refer to the correction system)
+ *       cpk_mex('kkt_destroy', k)
  *
  * Errors: every failure becomes mexErrMsgIdAndTxt after the call's temporaries are freed
  * (mexErrMsgIdAndTxt does not return: it unwinds to MATLAB, so the device matrices this call
@@ -37,6 +51,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "cpk.h"
@@ -100,6 +115,24 @@ static cpk_mat to_mat(const mxArray *a) {
 static cpk_pc to_pc(const mxArray *h) {
     if (!h || !mxIsUint64(h) || mxGetNumberOfElements(h) != 1) fail_msg("cpk:args", "bad handle");
     return (cpk_pc)(uintptr_t)(*(uint64_t *)mxGetData(h));
+}
+
+/* a kkt handle: the operator and the device matrices it follows, which must outlive it */
+typedef struct {
+    cpk_kkt K;
+    cpk_mat A, B, C;
+    int64_t N;
+} kkt_handle;
+
+static kkt_handle *to_kkt(const mxArray *h) {
+    if (!h || !mxIsUint64(h) || mxGetNumberOfElements(h) != 1) fail_msg("cpk:args", "bad handle");
+    return (kkt_handle *)(uintptr_t)(*(uint64_t *)mxGetData(h));
+}
+
+/* a dense real matrix with N rows */
+static void need_dense(const mxArray *a, int64_t N, const char *what) {
+    if (!a || mxIsSparse(a) || mxIsComplex(a) || (int64_t)mxGetM(a) != N)
+        fail_msg("cpk:dim", "%s: expected a dense real matrix with %lld rows", what, (long long)N);
 }
 
 /* opts struct -> cpk_opts, honouring isfield() (e.g. cpminres.m:98-111) */
@@ -192,7 +225,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     {   /* argument counts before anything is converted or a device is touched */
         static const struct { const char *cmd; int nrhs; } need[] = {
             {"pc_create", 4}, {"pc_set", 3}, {"pc_apply", 3}, {"pc_apply_ldl", 3}, {"pc_apply_multi", 3}, {"pc_divide", 3}, {"pc_destroy", 2}, {"pc_factor_report", 2},
-            {"method", 6}, {"reg_solve", 7}, {"method_solve_multi", 6}};
+            {"method", 6}, {"reg_solve", 7}, {"method_solve_multi", 6},
+            {"kkt_create", 4}, {"kkt_apply", 3}, {"kkt_residual", 4}, {"kkt_solve", 6}, {"kkt_destroy", 2}};
         int i;
         for (i = 0; i < (int)(sizeof need / sizeof need[0]); i++)
             if (!strcmp(cmd, need[i].cmd) && nrhs < need[i].nrhs)
@@ -346,6 +380,80 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         plhs[3] = mxCreateStructMatrix(1, 1, 1, ff);
         mxSetField(plhs[3], 0, "solved", solved);
         mxFree(s), mxFree(status);
+    } else if (!strcmp(cmd, "kkt_create")) {
+        cpk_mat A = to_mat(ARG(1)), B = to_mat(ARG(2)), C = to_mat(ARG(3));
+        kkt_handle *k;
+        cpk_kkt K = NULL;
+        int64_t info[8];
+        if ((st = cpk_kkt_create(ctx(), A, B, C, &K))) fail(st);
+        if ((st = cpk_kkt_get_info(K, info))) {
+            cpk_kkt_destroy(K);
+            fail(st);
+        }
+        k = malloc(sizeof *k);
+        if (!k) {
+            cpk_kkt_destroy(K);
+            fail_msg("cpk:error", "out of host memory");
+        }
+        k->K = K, k->A = A, k->B = B, k->C = C, k->N = info[0] + info[1];
+        g_ntmp = 0; /* the three matrices now belong to the handle */
+        plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
+        *(uint64_t *)mxGetData(plhs[0]) = (uint64_t)(uintptr_t)k;
+    } else if (!strcmp(cmd, "kkt_destroy")) {
+        kkt_handle *k = to_kkt(ARG(1));
+        if (k) {
+            cpk_kkt_destroy(k->K);
+            cpk_mat_destroy(k->A), cpk_mat_destroy(k->B), cpk_mat_destroy(k->C);
+            free(k);
+        }
+    } else if (!strcmp(cmd, "kkt_apply")) {
+        kkt_handle *k = to_kkt(ARG(1));
+        int64_t c, j;
+        need_dense(ARG(2), k->N, "Z");
+        c = (int64_t)mxGetN(ARG(2));
+        plhs[0] = mxCreateDoubleMatrix((mwSize)k->N, (mwSize)c, mxREAL);
+        for (j = 0; j < c && k->N > 0; j++)
+            if ((st = cpk_kkt_apply(k->K, mxGetPr(ARG(2)) + j * k->N, mxGetPr(plhs[0]) + j * k->N))) fail(st);
+    } else if (!strcmp(cmd, "kkt_residual")) {
+        kkt_handle *k = to_kkt(ARG(1));
+        const int64_t ld = k->N > 0 ? k->N : 1;
+        int64_t c;
+        mxArray *R, *sums;
+        need_dense(ARG(2), k->N, "Z");
+        need_dense(ARG(3), k->N, "B");
+        c = (int64_t)mxGetN(ARG(2));
+        if ((int64_t)mxGetN(ARG(3)) != c) fail_msg("cpk:dim", "B must have Z's %lld columns", (long long)c);
+        R = mxCreateDoubleMatrix((mwSize)k->N, (mwSize)c, mxREAL);
+        sums = mxCreateDoubleMatrix(4, (mwSize)c, mxREAL);
+        /* MATLAB stores a dense matrix column-major: the leading dimensions are the row count */
+        st = cpk_kkt_residual(k->K, c, mxGetPr(ARG(2)), ld, mxGetPr(ARG(3)), ld, mxGetPr(R), ld, mxGetPr(sums));
+        if (st) fail(st);
+        plhs[0] = R, plhs[1] = sums;
+    } else if (!strcmp(cmd, "kkt_solve")) {
+        kkt_handle *k = to_kkt(ARG(1));
+        const int mid = method_id(ARG(2));
+        cpk_pc M = to_pc(ARG(4));
+        const int warm = ARG(6) && !mxIsEmpty(ARG(6));
+        cpk_opts o;
+        cpk_stats s;
+        int64_t info[8];
+        mxArray *x, *res;
+        if ((st = cpk_kkt_get_info(k->K, info))) fail(st);
+        if (!ARG(3) || mxIsSparse(ARG(3)) || (int64_t)mxGetNumberOfElements(ARG(3)) != k->N)
+            fail_msg("cpk:dim", "b must have length %lld", (long long)k->N);
+        if (warm && (mxIsSparse(ARG(6)) || (int64_t)mxGetNumberOfElements(ARG(6)) != k->N))
+            fail_msg("cpk:dim", "x0 must have length %lld", (long long)k->N);
+        to_opts(ARG(5), &o);
+        alloc_hist(&s, mid, &o, info[0], info[1]);
+        x = mxCreateDoubleMatrix((mwSize)k->N, 1, mxREAL);
+        res = mxCreateDoubleMatrix(8, 1, mxREAL);
+        if (warm && k->N) memcpy(mxGetPr(x), mxGetPr(ARG(6)), (size_t)k->N * sizeof(double));
+        st = cpk_kkt_solve(k->K, mid, mxGetPr(ARG(3)), M, &o, mxGetPr(x), warm, &s, mxGetPr(res));
+        if (st) fail(st);
+        plhs[0] = x;
+        put_stats(mid, &s, &plhs[1], &plhs[2]);
+        plhs[3] = res;
+        free_hist(&s);
     } else {
         fail_msg("cpk:args", "cpk_mex: unknown command %s", cmd);
     }
