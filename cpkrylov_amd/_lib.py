@@ -16,7 +16,8 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 CPK_OK, CPK_ERR_INDEFINITE, CPK_ERR_DIM, CPK_ERR_ARGS, CPK_ERR_HIP, CPK_ERR_RCCL, CPK_ERR_FACTOR, \
-    CPK_ERR_NOMEM, CPK_ERR_UNSUPPORTED = range(9)
+    CPK_ERR_NOMEM, CPK_ERR_UNSUPPORTED, CPK_ERR_CALLBACK = range(10)
+CPK_OP_CAPTURABLE = 1
 COMM_KINDS = {0: "none", 1: "rccl", 2: "sim", 3: "null"}  # CPK_COMM_* (cpk_ctx_get_info)
 METHODS = {"cg": 0, "cglanczos": 1, "minres": 2, "symmlq": 3, "gmres": 4, "dqgmres": 5}
 _OPT_FIELDS = ("atol", "rtol", "btol", "itmax", "restart", "mem", "print",
@@ -60,6 +61,8 @@ class Profile(C.Structure):
 
 P = C.POINTER
 vp = C.c_void_p
+# cpk_op_fn: int fn(void *user, const double *d_x, double *d_y, int64_t n, void *stream)
+OpFn = C.CFUNCTYPE(C.c_int, vp, vp, vp, C.c_int64, vp)
 _SIGS = {
     "cpk_last_error": ([], C.c_char_p),
     "cpk_abi_version": ([], C.c_int),
@@ -74,6 +77,7 @@ _SIGS = {
     "cpk_mat_create_csr": ([vp, C.c_int64, C.c_int64, P(C.c_int64), P(C.c_int32), P(C.c_double), P(vp)], C.c_int),
     "cpk_mat_destroy": ([vp], C.c_int),
     "cpk_mat_spmv": ([vp, P(C.c_double), P(C.c_double)], C.c_int),
+    "cpk_mat_spmv_device": ([vp, vp, vp], C.c_int),
     "cpk_mat_set_values": ([vp, P(C.c_double), C.c_int64], C.c_int),
     "cpk_mat_set_values_device": ([vp, vp, C.c_int64], C.c_int),
     "cpk_mat_get_info": ([vp, P(C.c_int64)], C.c_int),
@@ -124,6 +128,15 @@ _SIGS = {
     "cpk_reg_solve": ([vp, C.c_int, P(C.c_double), vp, vp, vp, vp, P(Opts), P(C.c_double), P(Stats), P(vp)],
                       C.c_int),
     "cpk_reg_solve_device": ([vp, C.c_int, vp, vp, vp, vp, vp, P(Opts), vp, P(Stats)], C.c_int),
+    "cpk_op_create": ([vp, C.c_int64, OpFn, vp, C.c_int, P(vp)], C.c_int),
+    "cpk_op_destroy": ([vp], C.c_int),
+    "cpk_op_get_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_op_apply_device": ([vp, vp, vp], C.c_int),
+    "cpk_method_solve_op": ([vp, C.c_int, P(C.c_double), vp, vp, vp, P(Opts), P(C.c_double), P(C.c_double),
+                             P(Stats)], C.c_int),
+    "cpk_method_solve_op_device": ([vp, C.c_int, vp, vp, vp, vp, P(Opts), vp, P(Stats)], C.c_int),
+    "cpk_reg_solve_op": ([vp, C.c_int, P(C.c_double), vp, vp, vp, vp, P(Opts), P(C.c_double), P(Stats)], C.c_int),
+    "cpk_reg_solve_op_device": ([vp, C.c_int, vp, vp, vp, vp, vp, P(Opts), vp, P(Stats)], C.c_int),
     "cpk_kkt_create": ([vp, vp, vp, vp, P(vp)], C.c_int),
     "cpk_kkt_destroy": ([vp], C.c_int),
     "cpk_kkt_get_info": ([vp, P(C.c_int64)], C.c_int),

@@ -12,8 +12,9 @@ M = opLDL2(A,B,C); M.nitref = 1; y = M*z            M = opLDL2(A, B, C); M.nitre
 
 `opts` is a dict whose keys behave like MATLAB struct fields (absent = solver default).
 `stats` / `flag` are dicts with the reference's field names.  Matrices are scipy.sparse (or
-dense numpy) arrays; `A` must be an explicit matrix (a generic linear operator A is not
-supported on the device path).  Errors raise CpkError / IndefiniteError.
+dense numpy) arrays; `A` may also be an `Operator`, a product on device memory (the reference's
+"A may be a matrix or a linear operator"; a scipy LinearOperator works on host arrays and is
+refused).  Errors raise CpkError / IndefiniteError.
 """
 import ctypes as C
 import os
@@ -254,10 +255,111 @@ class Matrix:
 def _as_matrix(M, ctx):
     if isinstance(M, Matrix):
         return M
+    if isinstance(M, Operator):
+        raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "an Operator stands for A in a single-column solve only; "
+                       "B, C, G, the preconditioner's blocks and K's blocks must be matrices")
     if isinstance(M, sp.linalg.LinearOperator):
         raise CpkError(_lib.CPK_ERR_UNSUPPORTED,
-                       "A must be an explicit matrix on the device path (generic operators are out of scope)")
+                       "a scipy LinearOperator works on host arrays; wrap a device product in cpk.Operator")
     return Matrix(M, ctx)
+
+
+class _DeviceView:
+    """n float64 values at a device address, as __cuda_array_interface__ describes them (torch
+    takes writable views only, so the input's view is writable too: f must not write to x)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f8", "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class Operator:
+    """The (1,1) block A as a product on device memory (cpk_op): `fn(x_ptr, y_ptr, n, stream_ptr)`
+    enqueues y[0:n) = A @ x[0:n) (float64 device addresses as ints) on the HIP stream
+    `stream_ptr`, and returns None / 0, or nonzero to abort the solve.  The solvers take it where
+    they take the matrix A: cpcg ... cpdqgmres(b, A, C, M, opts) and
+    reg_cpkrylov(method, b, A, B, C, G, opts), one right-hand side, one GPU.
+
+    capturable=False (default): fn is called eagerly, once per Krylov product, and may do
+    anything on the stream; the solver runs one iteration per batch without graphs, so fn is
+    never called for an iteration that has already stopped.  capturable=True: fn may be called
+    while the stream is capturing -- it must only enqueue on `stream_ptr` (no synchronisation,
+    allocation or other stream) and what it enqueues may depend only on its arguments and on
+    device memory, because it is called once per captured iteration and replays do not call it.
+
+    An exception raised in fn aborts the solve: the CpkError (CPK_ERR_CALLBACK) the solve raises
+    carries it as __cause__.  A's symmetry is the caller's responsibility."""
+
+    def __init__(self, n, fn, ctx=None, capturable=False):
+        if not callable(fn):
+            raise CpkError(_lib.CPK_ERR_ARGS, "Operator: fn must be callable")
+        if int(n) != n or int(n) < 0:
+            raise CpkError(_lib.CPK_ERR_ARGS, "Operator: n must be an integer >= 0")
+        self.n, self.shape, self.capturable = int(n), (int(n), int(n)), bool(capturable)
+        self._fn, self._exc = fn, None
+
+        def trampoline(_user, x, y, nn, stream):
+            try:
+                rc = fn(x or 0, y or 0, nn, stream or 0)
+                return int(rc) if rc else 0
+            except BaseException as e:  # nothing may propagate through the C frames
+                self._exc = e
+                return -1
+
+        self._cb = _lib.OpFn(trampoline)  # kept alive with the handle
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(lib.cpk_op_create(self.ctx.h, self.n, self._cb, None, _lib.CPK_OP_CAPTURABLE if capturable else 0,
+                                C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_torch(cls, n, f, ctx=None):
+        """A from a torch function f(x: Tensor) -> Tensor (an autograd Hessian-vector product, a
+        dense mv, ...): x and the result's destination are zero-copy views of the engine's buffers
+        (__cuda_array_interface__), and f runs under torch.cuda.ExternalStream(stream_ptr), so its
+        kernels are ordered with the solver's.  Always non-capturable."""
+        import torch
+
+        views = {}
+
+        def fn(x_ptr, y_ptr, nn, stream_ptr):
+            if nn == 0:
+                return 0
+            key = (x_ptr, y_ptr, nn)
+            if key not in views:
+                views[key] = (torch.as_tensor(_DeviceView(x_ptr, nn), device="cuda"),
+                              torch.as_tensor(_DeviceView(y_ptr, nn), device="cuda"))
+            x, y = views[key]
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream_ptr)):
+                y.copy_(f(x))
+            return 0
+
+        return cls(n, fn, ctx=ctx, capturable=False)
+
+    def info(self):
+        """cpk_op_get_info: n, capturable, the calls of fn so far and those that returned nonzero."""
+        v = (C.c_int64 * 4)()
+        check(lib.cpk_op_get_info(self.h, v))
+        return {"n": v[0], "capturable": bool(v[1] & _lib.CPK_OP_CAPTURABLE), "calls": v[2], "failed": v[3]}
+
+    def _solve(self, call):
+        """Run one C solve entry; an exception fn raised becomes the cause of the solve's error."""
+        self._exc = None
+        rc = call()
+        if rc != _lib.CPK_OK:
+            exc, self._exc = self._exc, None
+            try:
+                check(rc)
+            except CpkError as e:
+                if exc is not None and rc == _lib.CPK_ERR_CALLBACK:
+                    raise e from exc
+                raise
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib.cpk_op_destroy(self.h)
+            self.h = None
 
 
 class opLDL2:
@@ -771,18 +873,25 @@ def _method(name):
         if not isinstance(M, opLDL2):
             raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
         ctx = M.ctx
-        Am, Cmat = _as_matrix(A, ctx), _as_matrix(Cm, ctx)
+        is_op = isinstance(A, Operator)
+        Am, Cmat = (A if is_op else _as_matrix(A, ctx)), _as_matrix(Cm, ctx)
         n, m = Am.shape[0], Cmat.shape[0]
         b = np.asarray(b, dtype=np.float64)
         if _is_block(b):
+            if is_op:
+                raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "an Operator takes one right-hand side; the block solve is matrix-only")
             return _method_block(name, b, Am, Cmat, M, opts, raise_on_error)
         b = np.ascontiguousarray(b).ravel()
         if b.shape[0] != n:
             raise CpkError(_lib.CPK_ERR_DIM, "b must have n entries")
         x, y = np.zeros(n), np.zeros(m)
         st, hist, lq, qr = _new_stats(_hist_cap(name, opts, n, m))
-        check(lib.cpk_method_solve(ctx.h, _lib.METHODS[name], _dptr(b), Am.h, Cmat.h, M.h,
-                                   C.byref(make_opts(opts)), _dptr(x), _dptr(y), C.byref(st)))
+        if is_op:
+            Am._solve(lambda: lib.cpk_method_solve_op(ctx.h, _lib.METHODS[name], _dptr(b), Am.h, Cmat.h, M.h,
+                                                      C.byref(make_opts(opts)), _dptr(x), _dptr(y), C.byref(st)))
+        else:
+            check(lib.cpk_method_solve(ctx.h, _lib.METHODS[name], _dptr(b), Am.h, Cmat.h, M.h,
+                                       C.byref(make_opts(opts)), _dptr(x), _dptr(y), C.byref(st)))
         stats, flag = _stats_from(name, st, hist, lq, qr)
         return x, y, stats, flag
 
@@ -795,7 +904,9 @@ def _method(name):
                    "X (n x k), Y (m x k) and stats, flag as lists of k dicts.  opts['print'] is ignored for a "
                    "block.  A column that hits the reference's indefinite stop raises CpkError carrying "
                    "`columns` (the per-column status codes) and `partial` (X, Y, stats, flag); with "
-                   "raise_on_error=False the results are returned with flag[j]['error'] set instead.")
+                   "raise_on_error=False the results are returned with flag[j]['error'] set instead.\n\n"
+                   "A may be an `Operator` (one right-hand side): the product A*v is then the operator's "
+                   "callback, everything else is unchanged.")
     return run
 
 
@@ -849,8 +960,43 @@ def _reg_block(name, b, mats, opts, ctx, raise_on_error):
     return X, stats, flags
 
 
+def _negated(Cmat, what):
+    """-C on the host from a Matrix handle's canonical CSR arrays (M = opLDL2(G, B, -C))."""
+    if Cmat._val is None:
+        raise CpkError(_lib.CPK_ERR_UNSUPPORTED, f"{what} builds -C on the host: C was last "
+                       "updated from device memory; pass its values with set_values from the host, or build "
+                       "M = opLDL2(G, B, -C) and call the method")
+    if Cmat._csc:
+        return sp.csc_matrix((-Cmat._val, Cmat._ind.astype(np.int64), Cmat._ptr.astype(np.int64)), shape=Cmat.shape)
+    return sp.csr_matrix((-Cmat._val, Cmat._ind, Cmat._ptr.astype(np.int64)), shape=Cmat.shape)
+
+
+def _reg_op(name, b, A, mats, opts, ctx):
+    """reg_cpkrylov with an Operator A: M = opLDL2(G, B, -C) with the preconditioner fields of opts
+    (reg_cpkrylov.m:128-148), then the shift (one call of A's fn when b(n+1:N) is not zero), the
+    method and the recovery on the device (cpk_reg_solve_op)."""
+    Bm, Cmat, Gm = mats
+    n, m = A.n, Bm.shape[0]
+    b = np.ascontiguousarray(b).ravel()
+    if b.shape[0] != n + m:
+        raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
+    M = opLDL2(Gm, Bm, _negated(Cmat, "reg_cpkrylov with an Operator"), ctx=ctx)
+    props = {k: opts[k] for k in _PC_PROPS if opts and k in opts}
+    if props:
+        M._set(**props)
+    x = np.zeros(n + m)
+    st, hist, lq, qr = _new_stats(_hist_cap(name, opts, n, m))
+    A._solve(lambda: lib.cpk_reg_solve_op(ctx.h, _lib.METHODS[name], _dptr(b), A.h, Bm.h, Cmat.h, M.h,
+                                          C.byref(make_opts(opts)), _dptr(x), C.byref(st)))
+    stats, flag = _stats_from(name, st, hist, lq, qr)
+    stats["ptime"], stats["stime"], stats["M"] = M.ptime, st.stime, M
+    return x, stats, flag
+
+
 def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None, raise_on_error=True):
     """[x, stats, flag] = reg_cpkrylov(method, b, A, B, C, G, opts)   (reg_cpkrylov.m:1-180).
+
+    A may be an `Operator` (one right-hand side, one GPU): M is built from G, B, C as always.
 
     An N x k array b with k != 1 is a block (cpcg and cpminres): M is built once and returned in
     stats[0]["M"], every column is shifted, solved and recovered as if alone, and x is N x k with
@@ -860,6 +1006,12 @@ def reg_cpkrylov(method, b, A, B, Cm, G, opts=None, ctx=None, raise_on_error=Tru
     name = getattr(method, "_cpk_method", method)
     if name not in _lib.METHODS:
         raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+    if isinstance(A, Operator):
+        ctx = ctx or A.ctx
+        b = np.asarray(b, dtype=np.float64)
+        if _is_block(b):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "an Operator takes one right-hand side; the block solve is matrix-only")
+        return _reg_op(name, b, A, [_as_matrix(M, ctx) for M in (B, Cm, G)], opts, ctx)
     ctx = ctx or default_context()
     mats = [_as_matrix(M, ctx) for M in (A, B, Cm, G)]
     n, m = mats[0].shape[0], mats[1].shape[0]
@@ -923,6 +1075,9 @@ class KKT:
     result goes to the device tensor passed as `out=` and nothing crosses PCIe but the sums."""
 
     def __init__(self, A, B, Cm, ctx=None):
+        if any(isinstance(M, Operator) for M in (A, B, Cm)):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K holds its blocks' entries: an Operator has none "
+                           "(use the solvers with the Operator, and check residuals with its own product)")
         first = next((M for M in (A, B, Cm) if isinstance(M, Matrix)), None)
         self.ctx = ctx or (first.ctx if first is not None else None) or default_context()
         self.A, self.B, self.C = (_as_matrix(M, self.ctx) for M in (A, B, Cm))
@@ -1034,6 +1189,8 @@ class KKT:
         name = getattr(method, "_cpk_method", method)
         if name not in _lib.METHODS:
             raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+        if any(isinstance(v, Operator) for v in (b, M, x0, out)):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.solve is matrix-only: K's (1,1) block is the matrix it was built on")
         if not isinstance(M, opLDL2):
             raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
         st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))

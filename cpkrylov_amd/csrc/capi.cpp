@@ -146,6 +146,42 @@ struct cpk_mat_s {
     }
 };
 
+// The operator-valued A: the caller's callback, and blkdiag(0, C) -- n empty rows, then C's rows
+// with their columns moved past n -- keyed by C's generation as cpk_mat_s::ac is.  Its value
+// array is C's values, so an update of C is one copy at the next use, to the same address.
+struct cpk_op_s {
+    cpk_ctx_s *ctx = nullptr;
+    int64_t n = 0;
+    cpk_op_fn fn = nullptr;
+    void *user = nullptr;
+    int flags = 0;
+    uint64_t gen = 0;
+    int64_t calls = 0, fails = 0;
+    std::map<uint64_t, KrylovOp> zc;
+    OpHook hook() { return OpHook{fn, user, gen, flags, &calls, &fails, nullptr, nullptr}; }
+    const DMat &krylov_op(cpk_mat_s *C) {
+        auto it = zc.find(C->gen);
+        if (it == zc.end()) {
+            HCsr Z;
+            Z.nrows = Z.ncols = n;
+            Z.ptr.assign((size_t)n + 1, 0);
+            KrylovOp op;
+            op.vc = C->vgen;
+            op.m = std::make_unique<DMat>();
+            make_dmat(blkdiag(Z, C->host()), *op.m);
+            it = zc.emplace(C->gen, std::move(op)).first;
+        }
+        KrylovOp &op = it->second;
+        if (op.vc != C->vgen) {
+            DMat &m = *op.m;
+            if (m.nnz != C->h.nnz() || m.nrows != n + C->h.nrows || (int64_t)m.val.n != m.nnz)
+                throw Error(CPK_ERR_ARGS, "blkdiag(0, C): the cached operator does not hold C's entries");
+            C->refresh_half(ctx->c, C, m.val.p), op.vc = C->vgen;
+        }
+        return *op.m;
+    }
+};
+
 // K = [A B'; B -C] on the device in assemble_kp's entry order, with the handles' generations it
 // holds and the map from their stored values (kp_value_sources' order) to its value array
 struct cpk_kkt_s {
@@ -525,6 +561,14 @@ int cpk_mat_spmv(cpk_mat A, const double *x, double *y) {
     API_END
 }
 
+int cpk_mat_spmv_device(cpk_mat A, const double *d_x, double *d_y) {
+    API_BEGIN
+    need(A && (d_x || !A->h.ncols) && (d_y || !A->h.nrows), "NULL argument");
+    const DMat &d = A->dev();  // refuses a host-only matrix
+    launch_spmv(A->ctx->c, d, d_x, d_y, nullptr);
+    API_END
+}
+
 int cpk_pc_create(cpk_ctx ctx, cpk_mat A11, cpk_mat B, cpk_mat C22, double *ptime, cpk_pc *out) {
     API_BEGIN
     need(ctx && A11 && B && C22 && out, "opLDL2: Invalid number of arguments.");
@@ -898,6 +942,114 @@ int cpk_reg_shift_device(cpk_ctx ctx, const double *d_b, cpk_mat A, cpk_mat B, c
     const ShiftOps so = shift_ops(A, C, *M->p);
     int s = reg_shift_device(ctx->c, d_b, *so.A, *so.Bt, so.bt_colmin, *M->p, d_b1, d_xy0);
     if (shifted) *shifted = s;
+    API_END
+}
+
+// ---- the operator-valued A (cpk_op) ----------------------------------------------------------
+int cpk_op_create(cpk_ctx ctx, int64_t n, cpk_op_fn fn, void *user, int flags, cpk_op *out) {
+    API_BEGIN
+    need(ctx && out, "NULL argument");
+    if (n < 0) throw Error(CPK_ERR_DIM, "op: n must be >= 0");
+    need((flags & ~CPK_OP_CAPTURABLE) == 0, "op: unknown flags");
+    auto a = std::make_unique<cpk_op_s>();
+    a->ctx = ctx, a->n = n, a->fn = fn, a->user = user, a->flags = flags;
+    a->gen = g_gen++;
+    *out = a.release();
+    API_END
+}
+
+int cpk_op_destroy(cpk_op A) {
+    API_BEGIN
+    delete A;
+    API_END
+}
+
+int cpk_op_get_info(cpk_op A, int64_t info[4]) {
+    API_BEGIN
+    need(A && info, "NULL argument");
+    info[0] = A->n, info[1] = A->flags, info[2] = A->calls, info[3] = A->fails;
+    API_END
+}
+
+int cpk_op_apply_device(cpk_op A, const double *d_x, double *d_y) {
+    API_BEGIN
+    need(A && ((d_x && d_y) || !A->n), "NULL argument");
+    need(A->fn != nullptr, "op: the callback is NULL");
+    op_call(A->ctx->c, A->hook(), d_x, d_y, A->n);
+    API_END
+}
+
+// what every operator solve refuses, before anything is written
+static void check_op_solve(cpk_ctx ctx, cpk_op A, cpk_mat C, const cpk_pc_s *M) {
+    need(ctx && A && C && M, "NULL argument");
+    need(A->fn != nullptr, "op: the callback is NULL");
+    need(A->ctx == ctx && M->ctx == ctx && C->ctx == ctx, "op: the operator, C and M belong to one context");
+    if (ctx->c.dist() || M->p->dist)
+        throw Error(CPK_ERR_UNSUPPORTED, "an operator-valued A is single-GPU (a distributed context keeps row slices of A)");
+    if (C->h.nrows != C->h.ncols) throw Error(CPK_ERR_DIM, "C must be square");
+    if (A->n != M->p->gn || C->h.nrows != M->p->gm) throw Error(CPK_ERR_DIM, "A, C and M dimensions disagree");
+}
+
+int cpk_method_solve_op_device(cpk_ctx ctx, int method, const double *d_b, cpk_op A, cpk_mat C, cpk_pc M,
+                               const cpk_opts *opts, double *d_xy, cpk_stats *stats) {
+    API_BEGIN
+    check_op_solve(ctx, A, C, M);
+    need((d_xy || !M->p->N) && (d_b || !M->p->n), "NULL argument");
+    const OpHook h = A->hook();
+    method_solve_device(ctx->c, method, d_b, A->krylov_op(C), *M->p, opts, d_xy, stats, &h);
+    API_END
+}
+
+int cpk_method_solve_op(cpk_ctx ctx, int method, const double *b, cpk_op A, cpk_mat C, cpk_pc M, const cpk_opts *opts,
+                        double *x, double *y, cpk_stats *stats) {
+    API_BEGIN
+    check_op_solve(ctx, A, C, M);
+    need(b && x && (y || !C->h.nrows), "NULL argument");
+    Ctx &c = ctx->c;
+    Precond &p = *M->p;
+    const int64_t n = p.n, m = p.m, N = n + m;
+    const OpHook h = A->hook();
+    const DMat &ZC = A->krylov_op(C);
+    DBuf<double> db, dxy;
+    h2d(db, b, (size_t)n);
+    dxy.alloc((size_t)std::max<int64_t>(N, 1));
+    auto t0 = std::chrono::steady_clock::now();
+    method_solve_device(c, method, db.p, ZC, p, opts, dxy.p, stats, &h);
+    if (n) CPK_HIP(hipMemcpy(x, dxy.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (m) CPK_HIP(hipMemcpy(y, dxy.p + n, m * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    API_END
+}
+
+int cpk_reg_solve_op_device(cpk_ctx ctx, int method, const double *d_b, cpk_op A, cpk_mat B, cpk_mat C, cpk_pc M,
+                            const cpk_opts *opts, double *d_x, cpk_stats *stats) {
+    API_BEGIN
+    check_op_solve(ctx, A, C, M);
+    need(B && ((d_b && d_x) || !M->p->N), "NULL argument");
+    Precond &p = *M->p;
+    const OpHook h = A->hook();
+    const DMat &ZC = A->krylov_op(C);
+    // the shift's B'*xy0(n+1:N): rows < n of Kp, columns >= n; A's rows are the callback's
+    reg_solve_device(ctx->c, method, d_b, ZC, ZC, p.dKp, p.n, p, opts, d_x, stats, &h);
+    if (stats) stats->ptime = p.ptime;
+    API_END
+}
+
+int cpk_reg_solve_op(cpk_ctx ctx, int method, const double *b, cpk_op A, cpk_mat B, cpk_mat C, cpk_pc M,
+                     const cpk_opts *opts, double *x, cpk_stats *stats) {
+    API_BEGIN
+    check_op_solve(ctx, A, C, M);
+    need(B && b && x, "NULL argument");
+    Precond &p = *M->p;
+    const int64_t N = p.N;
+    const OpHook h = A->hook();
+    const DMat &ZC = A->krylov_op(C);
+    DBuf<double> db, dx;
+    h2d(db, b, (size_t)N);
+    dx.alloc((size_t)std::max<int64_t>(N, 1));
+    reg_solve_device(ctx->c, method, db.p, ZC, ZC, p.dKp, p.n, p, opts, dx.p, stats, &h);
+    if (N) CPK_HIP(hipMemcpy(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost));
+    if (stats) stats->ptime = p.ptime;
     API_END
 }
 

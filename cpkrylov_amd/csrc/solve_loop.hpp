@@ -157,6 +157,7 @@ struct SolveDriver {
     double atol = 1e-6, rtol = 1e-6, btol = 0, itmax = 0;
     int batch = 16;
     bool use_graph = true;
+    bool single_step = false;  // every batch is one iteration (an operator-valued A called eagerly)
     GraphCache graphs;
     DBuf<DState> dst;     // a state per column: nstates travel between host and device,
     DState hs[kMultiKP];  // the first kc of a call are live
@@ -172,6 +173,7 @@ struct SolveDriver {
             if (o->has_itmax) itmax = o->itmax;
         }
         use_graph = !c.opts.no_graph;
+        single_step = false;
         batch = c.opts.batch > 0 ? c.opts.batch : 16;
     }
     // the fields every column's state starts from (all others zero)
@@ -207,7 +209,7 @@ struct SolveDriver {
         int64_t guard = 0;
         for (int j = 0; j < kc; j++) guard = std::max(guard, hs[j].k);
         guard += (int64_t)std::min(itmax, 4.0e9) + 2 * batch + 2;
-        BatchPlan plan{pow2_at_least(batch, 64), c.opts.batch <= 0, itmax};
+        BatchPlan plan{single_step ? 1 : pow2_at_least(batch, 64), c.opts.batch <= 0, itmax};
         int b = plan.base;
         for (;;) {
             plan.before(hs, kc);

@@ -258,4 +258,61 @@ struct EpiKrylov {
     }
 };
 
+// The operator-valued A (cpk_op): u = A*vk comes from the caller's callback, which needs its
+// input at an address the host knows, while the policies pick theirs from the device-resident
+// st->k.  So the product takes three steps: this copy of the selected vector's x-part to the
+// solver's fixed XIN, the callback XIN -> UOP, and spmv_stream<EpiKrylovOp> below.
+// The copy has none of F::skip()'s side effects and runs whether or not the solve has stopped:
+// XIN and UOP are scratch, and what F::select reads then is still inside its ring (st->k stays
+// at most one past the last running iteration: a slot of 3, a position of the DQGMRES ring, or
+// column k <= restart of GMRES's restart + 1).
+template <class F>
+__global__ __launch_bounds__(kBlock) void krylov_op_gather_kernel(F f, DState *st, double *__restrict__ xin, int64_t n) {
+    const double *x = f.select(st, nullptr);
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) xin[i] = x[i];
+}
+// EpiKrylov over blkdiag(0, C): n empty rows, then C's.  A row r < n takes the callback's u[r]
+// in place of its (empty) row sum; a row r >= n is EpiKrylov's.  skip() / running, select, the two
+// inner products split at n and fin(st, tot) are EpiKrylov's, so a stopped solve writes nothing.
+// 5 waves per SIMD: 82-84 VGPRs and no scratch; at EpiKrylov's 6 (<= 80 VGPRs) the extra pointer
+// costs 2-4 spilled VGPRs (12-20 bytes of scratch per lane)
+#ifndef CPK_SPMV_OP_WAVES
+#define CPK_SPMV_OP_WAVES 5
+#endif
+template <class F, class A = double>
+struct EpiKrylovOp {
+    static_assert(!F::kNorm, "an operator solve runs cpminres's unfused sequence");
+    DState *st;
+    const double *xsel;  // resolved input vector
+    double *y;
+    int64_t n;
+    RedBuf rb;
+    F f;
+    const double *uop;  // the callback's output, n values
+    A dn{}, dm{};
+    static constexpr int kWaves = std::is_same<A, XAcc>::value ? 4 : CPK_SPMV_OP_WAVES;
+    __device__ bool skip() { return f.skip(st); }
+    __device__ const double *xvec(const double *base) {
+        xsel = f.select(st, base);
+        acc_init(dn, rb.xsub, 0, 2), acc_init(dm, rb.xsub, 1, 2);
+        return xsel;
+    }
+    __device__ double pre(int64_t r) const { return xsel[r]; }
+    __device__ void row(int64_t r, double acc, double xr) {
+        if (r < n) {
+            acc = uop[r];
+            y[r] = acc;
+            dadd(dn, acc, xr);
+        } else {
+            y[r] = acc;
+            dadd(dm, acc, xr);
+        }
+    }
+    __device__ void finish() {
+        A v[2] = {dn, dm};
+        double tot[2];
+        if (grid_sum<2>(v, rb, tot) && threadIdx.x == 0) f.fin(st, tot);
+    }
+};
+
 }  // namespace cpk

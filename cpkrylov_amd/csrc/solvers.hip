@@ -253,9 +253,33 @@ void launch_krylov_spmv_as(Ctx &c, const DMat &AC, DState *st, double *y, int64_
                            AC.val.p, AC.blk.p, AC.nblk, (const double *)nullptr, (int64_t)0, e,
                            (const double *)nullptr, (int64_t)0);
 }
+// the operator-valued A: the selected vector's x-part to XIN, the callback XIN -> UOP, then the
+// gated product over AC = blkdiag(0, C) whose rows < n take UOP (solver_common.hpp)
+template <class P, class A>
+void launch_krylov_op_as(Ctx &c, const DMat &AC, DState *st, double *y, int64_t n, const P &pol, const OpHook &op) {
+    using E = EpiKrylovOp<P, A>;
+    E e{st, nullptr, y, n, red_buf(c), pol, op.uop};
+    hipLaunchKernelGGL((spmv_stream<E, false>), dim3(spmv_grid<E, false>(AC.nblk)), dim3(kBlock), 0, c.stream, AC.ptr.p,
+                       AC.col.p, AC.val.p, AC.blk.p, AC.nblk, (const double *)nullptr, (int64_t)0, e,
+                       (const double *)nullptr, (int64_t)0);
+}
+template <class P>
+void launch_krylov_op(Ctx &c, const DMat &AC, DState *st, double *y, int64_t n, const P &pol, const OpHook &op) {
+    if constexpr (P::kNorm) {
+        throw Error(CPK_ERR_ARGS, "internal: the fused cpminres update on an operator-valued A");
+    } else {
+        if (c.dist() || AC.halo()) throw Error(CPK_ERR_UNSUPPORTED, "an operator-valued A on a distributed context");
+        if (n > 0)
+            hipLaunchKernelGGL(krylov_op_gather_kernel<P>, dim3(ew_grid(n)), dim3(kBlock), 0, c.stream, pol, st, op.xin, n);
+        op_call(c, op, op.xin, op.uop, n);
+        if (c.exact()) launch_krylov_op_as<P, XAcc>(c, AC, st, y, n, pol, op);
+        else launch_krylov_op_as<P, double>(c, AC, st, y, n, pol, op);
+    }
+}
 template <class P>
 void launch_krylov_spmv(Ctx &c, const DMat &AC, DState *st, double *y, int64_t n, const P &pol, bool defer = false,
-                        bool halo_ready = false) {
+                        bool halo_ready = false, const OpHook *op = nullptr) {
+    if (op) return launch_krylov_op(c, AC, st, y, n, pol, *op);
     const bool dist = c.dist();
     if (defer && c.exact()) throw Error(CPK_ERR_ARGS, "internal: deferred Krylov partials in exact mode");
     if (AC.halo() && AC.kmax > 0 && !halo_ready) launch_krylov_halo(c, AC, st, pol);
@@ -1516,9 +1540,19 @@ struct SolveCore : SolveDriver {
     // reused across calls
     std::vector<DBuf<double>> rings;
     size_t ring_next = 0;
+    // the operator-valued A (op.fn != nullptr): the callback and this solver's XIN and UOP, whose
+    // addresses the callback sees for as long as the solver is cached
+    OpHook op;
+    DBuf<double> xin, uop;
+    const OpHook *opp() const { return op.fn ? &op : nullptr; }
 
-    SolveCore(Ctx &cc, Precond &MM, const DMat &ACm, int meth, const cpk_opts *o)
+    SolveCore(Ctx &cc, Precond &MM, const DMat &ACm, int meth, const cpk_opts *o, const OpHook *oph = nullptr)
         : SolveDriver(cc, 1), M(MM), AC(ACm), n(MM.n), m(MM.m), N(MM.N), method(meth) {
+        if (oph) {
+            op = *oph;
+            xin.alloc((size_t)std::max<int64_t>(n, 1)), uop.alloc((size_t)std::max<int64_t>(n, 1));
+            op.xin = xin.p, op.uop = uop.p;
+        }
         reset(o);
     }
     // per-call options (they only reach the device through DState, not through captured kernels)
@@ -1531,6 +1565,9 @@ struct SolveCore : SolveDriver {
             if (o->has_print) print = o->print != 0;
         }
         if (c.dist() && !(c.comm->capturable() && c.opts.dist_graph)) use_graph = false;
+        // a callback that may not be captured: eager batches of one iteration, so it is never
+        // called for an iteration that has already stopped and its call count is exact
+        if (op.fn && !op.capturable()) use_graph = false, single_step = true;
         if (c.rank != 0) print = false;
         printed = 0;
         ring_next = 0;
@@ -1720,7 +1757,7 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
     launch_set_concat(c, UT, b, n, m);
     M.apply(UT, N, VPREC, nullptr);
     // cpminres, fused update (below): v1 unnormalised in RAW as well, for the first product
-    double *RAW = kind == 0 && !c.opts.no_minres_fuse ? vec(2) : nullptr;
+    double *RAW = kind == 0 && !c.opts.no_minres_fuse && !op.fn ? vec(2) : nullptr;  // an operator-valued A: unfused
     if (kind == 0)
         launch_ewred<1>(c, N, InitLanczos<0>{st, VPREC, b, VQ + N, VQ, W + 2 * N, xy, n});
     else if (kind == 1)
@@ -1750,11 +1787,11 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
             if (hmerge) launch_krylov_halo(c, AC, st, pol);  // v1's halo, before the first iteration
             auto body = [&]() {
                 if (piggy) {
-                    launch_krylov_spmv(c, AC, st, UT, n, pol, true, hmerge);
+                    launch_krylov_spmv(c, AC, st, UT, n, pol, true, hmerge, opp());
                     M.apply(UT, n, VPREC, &st->running, c.red.p);
                     if (!hmerge) launch_krylov_fin_sep(c, M.sep, st, pol);  // else in the Lanczos step
                 } else {
-                    launch_krylov_spmv(c, AC, st, UT, n, pol);
+                    launch_krylov_spmv(c, AC, st, UT, n, pol, false, false, opp());
                     M.apply(UT, n, VPREC, &st->running);
                 }
                 LanczosStep<0> ls{st, VQ, VPREC, UT, xy, W, n, N, 0, 2, 1};
@@ -1800,7 +1837,7 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
             printed = (int64_t)v.size();
         };
         auto body = [&]() {
-            launch_krylov_spmv(c, AC, st, UT, n, PolLanczosSpmv<1>{VQ, N, 0});
+            launch_krylov_spmv(c, AC, st, UT, n, PolLanczosSpmv<1>{VQ, N, 0}, false, false, opp());
             M.apply(UT, n, VPREC, &st->running);
             launch_ewred<2>(c, N, LanczosStep<1>{st, VQ, VPREC, UT, xy, W, n, N, 0, 2, 1});
             launch_ew(c, N, CglUpdate{st, VQ, W, N});
@@ -1831,7 +1868,7 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
         }
         if (h.flag != 2) {
             // pre-step: second Lanczos vector (cpsymmlq.m:193-225), vk = VQ[1], vkp1 -> VQ[2]
-            launch_krylov_spmv(c, AC, st, UT, n, PolPlainSpmv{VQ + N});
+            launch_krylov_spmv(c, AC, st, UT, n, PolPlainSpmv{VQ + N}, false, false, opp());
             M.apply(UT, n, VPREC, nullptr);
             launch_ewred<2>(c, N, SymmlqPre{st, VQ + N, VPREC, UT, VQ + 2 * N, n});
             launch_ew(c, N, NormalizeCopy{st, VQ + 2 * N, nullptr, 0, 0.0});
@@ -1848,7 +1885,7 @@ void SolveCore::minres_like(int kind, const double *b, double *xy, cpk_stats *st
                 printed = (int64_t)cgv.size();
             };
             auto body = [&]() {
-                launch_krylov_spmv(c, AC, st, UT, n, PolLanczosSpmv<2>{VQ, N, 1});
+                launch_krylov_spmv(c, AC, st, UT, n, PolLanczosSpmv<2>{VQ, N, 1}, false, false, opp());
                 M.apply(UT, n, VPREC, &st->running);
                 launch_ewred<2>(c, N, LanczosStep<2>{st, VQ, VPREC, UT, xy, W, n, N, 1, 0, 2});
                 launch_ew(c, N, SymmlqUpdate{st, VQ, W, xy, n, N});
@@ -1902,7 +1939,7 @@ void SolveCore::cg(const double *b, double *xy, cpk_stats *stats) {
         printed = (int64_t)v.size();
     };
     auto body = [&]() {
-        launch_krylov_spmv(c, AC, st, APCQ, n, PolCgSpmv{PQ});
+        launch_krylov_spmv(c, AC, st, APCQ, n, PolCgSpmv{PQ}, false, false, opp());
         launch_ew(c, N, CgStep{st, XA, GW, PQ, APCQ});
         M.apply(GW, N, RU, &st->running);
         launch_ewred<2>(c, N, CgResid{st, XA, RU, GW, TT, n});
@@ -1937,6 +1974,11 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
             M.apply(UT, n, Wv, nullptr);        // M * [u; -t]
         } else {
             launch_spmv(c, AC, xy, TMP, nullptr);  // [A*x; C*y]
+            if (op.fn) {  // AC's first n rows are empty: A*x by one call, outside every capture
+                if (n) CPK_HIP(hipMemcpyAsync(op.xin, xy, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+                op_call(c, op, op.xin, op.uop, n);
+                if (n) CPK_HIP(hipMemcpyAsync(TMP, op.uop, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+            }
             launch_ew(c, N, GmresRestartRhs{b, TMP, UT, n});
             M.apply(UT, n, Wv, nullptr);
         }
@@ -1952,7 +1994,7 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
         }
         const int64_t base = (outer - 1) * R, hist0 = h.nh;
         auto body = [&]() {
-            launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, 0});
+            launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, 0}, false, false, opp());
             M.apply(UT, n, Wv, &st->running);
             launch_arnoldi_dots(c, st, V, Wv, UT, n, N, 0, R);
             launch_ewtred<2>(c, N, ArnoldiOrth{st, V, UT, n, N, 0, Window{}, nullptr});
@@ -2024,7 +2066,7 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
     if (prof) use_graph = false;
     auto body = [&]() {
         if (prof) mark();
-        launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, M1});
+        launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, M1}, false, false, opp());
         if (prof) mark();
         M.apply(UT, n, Wv, &st->running);
         if (prof) mark();
@@ -2070,23 +2112,25 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
 // ==============================================================================================
 // The cached solver of (method, operators, vectors, captured properties); see SolveCore.
 static std::string solver_key(const Ctx &c, const Precond &M, const DMat &AC, int method, const cpk_opts *o,
-                              const double *d_b, const double *d_xy) {
-    char buf[512];
+                              const double *d_b, const double *d_xy, const OpHook *op) {
+    char buf[640];
     const double restart = o && o->has_restart ? o->restart : 50, mem = o && o->has_mem ? o->mem : 50;
     const double itmax = o && o->has_itmax ? o->itmax : -1;
     // the context's engine options enter through their hash (graphs captured under one set of
     // options are not replayed under another)
-    snprintf(buf, sizeof buf, "%d|%llu|%p|%p|%p|%p|%p|%.17g|%.17g|%.17g|%d|%.17g|%.17g|%.17g|%llx", method,
+    // an operator-valued A: its generation and flags (a capturable and an eager solver differ)
+    snprintf(buf, sizeof buf, "%d|%llu|%p|%p|%p|%p|%p|%.17g|%.17g|%.17g|%d|%.17g|%.17g|%.17g|%llx|%llu|%d", method,
              (unsigned long long)AC.gen, (const void *)d_b, (const void *)d_xy, (const void *)c.partials.p,
              (const void *)c.counter.p, (const void *)c.red.p, M.nitref, M.force_itref, M.itref_tol,
              (M.residual_update != 0 && M.handle) ? 1 : 0, restart, mem,
-             method == CPK_DQGMRES ? itmax : 0.0, (unsigned long long)engine_opts_hash(c.opts));
+             method == CPK_DQGMRES ? itmax : 0.0, (unsigned long long)engine_opts_hash(c.opts),
+             (unsigned long long)(op ? op->gen : 0), op ? op->flags : 0);
     return buf;
 }
 
 static SolveCore &solver_for(Ctx &c, Precond &M, const DMat &AC, int method, const cpk_opts *opts,
-                             const double *d_b = nullptr, const double *d_xy = nullptr) {
-    const std::string key = solver_key(c, M, AC, method, opts, d_b, d_xy);
+                             const double *d_b = nullptr, const double *d_xy = nullptr, const OpHook *op = nullptr) {
+    const std::string key = solver_key(c, M, AC, method, opts, d_b, d_xy, op);
     for (auto &e : M.solvers)
         if (e.first == key) {
             auto *s = static_cast<SolveCore *>(e.second.get());
@@ -2094,16 +2138,17 @@ static SolveCore &solver_for(Ctx &c, Precond &M, const DMat &AC, int method, con
             return *s;
         }
     if (M.solvers.size() >= 4) M.solvers.erase(M.solvers.begin());  // bounded: oldest out
-    std::shared_ptr<void> sp(new SolveCore(c, M, AC, method, opts));
+    std::shared_ptr<void> sp(new SolveCore(c, M, AC, method, opts, op));
     M.solvers.emplace_back(key, sp);
     return *static_cast<SolveCore *>(sp.get());
 }
 
 void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, Precond &M, const cpk_opts *opts,
-                         double *d_xy, cpk_stats *stats) {
+                         double *d_xy, cpk_stats *stats, const OpHook *op) {
     if (method < CPK_CG || method > CPK_DQGMRES) throw Error(CPK_ERR_ARGS, "unknown method");
+    if (op && (c.dist() || M.dist)) throw Error(CPK_ERR_UNSUPPORTED, "an operator-valued A on a distributed context");
     CPK_HIP(hipEventRecord(c.ev0, c.stream));
-    SolveCore &s = solver_for(c, M, AC, method, opts, d_b, d_xy);
+    SolveCore &s = solver_for(c, M, AC, method, opts, d_b, d_xy, op);
     s.nbatch = 0;
     if (s.agreeing()) {  // a rank that fails before the solve's first collective stops every rank
         std::exception_ptr local;
@@ -2133,7 +2178,7 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
         float ms = 0;
         CPK_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
         stats->loop_ms = ms;
-        stats->bytes_moved = method_bytes(method, AC, M, stats->niters, opts);
+        stats->bytes_moved = method_bytes(method, AC, M, stats->niters, opts, op);
     }
 }
 
@@ -2142,8 +2187,9 @@ void launch_recover(Ctx &c, int64_t N, const double *d_x0, const double *d_dx, d
     launch_ew(c, N, Recover{d_x0, d_dx, d_x});
 }
 
-int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
-                     double *d_b1, double *d_xy0) {
+// op: A*xy0(1:n) by one direct call of its callback (Arows is then null)
+static int reg_shift(Ctx &c, const double *d_b, const DMat *Arows, const OpHook *op, const DMat &Btrows, int64_t bt_colmin,
+                     Precond &M, double *d_b1, double *d_xy0) {
     const int64_t n = M.n, m = M.m, N = M.N;
     DBuf<int> flag;
     flag.alloc(1);
@@ -2162,7 +2208,8 @@ int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &B
         if (n) CPK_HIP(hipMemsetAsync(t1.p, 0, n * sizeof(double), c.stream));
         if (m) CPK_HIP(hipMemcpyAsync(t1.p + n, d_b + n, m * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
         M.apply(t1.p, N, d_xy0, nullptr);
-        launch_spmv(c, Arows, d_xy0, t1.p, nullptr);                     // rows < n: A*xy0(1:n)
+        if (op) op_call(c, *op, d_xy0, t1.p, n);                         // A*xy0(1:n)
+        else launch_spmv(c, *Arows, d_xy0, t1.p, nullptr);               // rows < n: A*xy0(1:n)
         launch_spmv_colmask(c, Btrows, bt_colmin, d_xy0, t2.p, nullptr);  // rows < n: B'*xy0(n+1:N)
         launch_ew(c, n, ShiftRhs{d_b, t1.p, t2.p, d_b1});  // b1 = b(1:n) - A*xy0(1:n) - B'*xy0(n+1:N)
         CPK_HIP(hipStreamSynchronize(c.stream));
@@ -2173,14 +2220,26 @@ int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &B
     return shift;
 }
 
+int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
+                     double *d_b1, double *d_xy0) {
+    return reg_shift(c, d_b, &Arows, nullptr, Btrows, bt_colmin, M, d_b1, d_xy0);
+}
+int reg_shift_device(Ctx &c, const double *d_b, const OpHook &op, const DMat &Btrows, int64_t bt_colmin, Precond &M,
+                     double *d_b1, double *d_xy0) {
+    if (c.dist() || M.dist) throw Error(CPK_ERR_UNSUPPORTED, "an operator-valued A on a distributed context");
+    return reg_shift(c, d_b, nullptr, &op, Btrows, bt_colmin, M, d_b1, d_xy0);
+}
+
 void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, const DMat &Arows, const DMat &Btrows,
-                      int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats) {
+                      int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats,
+                      const OpHook *op) {
     const int64_t n = M.n, N = M.N;
     auto t0 = std::chrono::steady_clock::now();
     DBuf<double> xy0, b1, dxy;
     xy0.alloc(std::max<int64_t>(N, 1)), b1.alloc(std::max<int64_t>(n, 1)), dxy.alloc(std::max<int64_t>(N, 1));
-    const int shift = reg_shift_device(c, d_b, Arows, Btrows, bt_colmin, M, b1.p, xy0.p);
-    method_solve_device(c, method, b1.p, AC, M, opts, shift ? dxy.p : d_x, stats);
+    const int shift = op ? reg_shift_device(c, d_b, *op, Btrows, bt_colmin, M, b1.p, xy0.p)
+                         : reg_shift_device(c, d_b, Arows, Btrows, bt_colmin, M, b1.p, xy0.p);
+    method_solve_device(c, method, b1.p, AC, M, opts, shift ? dxy.p : d_x, stats, op);
     if (shift) launch_ew(c, N, Recover{xy0.p, dxy.p, d_x});  // x = [xy0(1:n) + dx; xy0(n+1:N) + dy]
     CPK_HIP(hipStreamSynchronize(c.stream));
     if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -2327,15 +2386,17 @@ void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *
 
 // Algorithmic HBM bytes of one method call: per iteration the Krylov SpMV,
 // the preconditioner apply and the streaming vector kernels, counted as ideal single touches.
-double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts) {
+double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts,
+                    const OpHook *op) {
     const double N = (double)M.N;
-    const double spmv = 12.0 * AC.nnz + 4.0 * (N + 1) + 8.0 * N /*x*/ + 8.0 * N /*y*/;
+    // an operator-valued A: AC is blkdiag(0, C), plus the gather (16 n) and the read of fn's output (8 n)
+    const double spmv = 12.0 * AC.nnz + 4.0 * (N + 1) + 8.0 * N /*x*/ + 8.0 * N /*y*/ + (op ? 24.0 * M.n : 0.0);
     const double mapply = M.apply_bytes();
     double vec = 0;
     switch (method) {
     case CPK_MINRES:  // lanczos step (5 streams) + update (8 streams); fused: the step with the update
         // (10 streams) and the normalised vector the Krylov product stores (1)
-        vec = 8 * N * (M.ctx && !M.ctx->opts.no_minres_fuse ? 10 + 1 : 5 + 8);
+        vec = 8 * N * (M.ctx && !M.ctx->opts.no_minres_fuse && !op ? 10 + 1 : 5 + 8);
         break;
     case CPK_CGLANCZOS: vec = 8 * N * (7 + 4); break;
     case CPK_SYMMLQ: vec = 8 * N * (5 + 7); break;

@@ -3,15 +3,44 @@
 #include "dev.hpp"
 
 namespace cpk {
+// The operator-valued A (cpk_op): the caller's product y(0:n) = A*x(0:n), the
+// handle's generation and flags (both enter the solver key) and its two call counters.  xin / uop:
+// the fixed-address input and output of the per-iteration product, owned by the cached solver.
+// fn == nullptr: A is the matrix inside AC.
+struct OpHook {
+    cpk_op_fn fn = nullptr;
+    void *user = nullptr;
+    uint64_t gen = 0;
+    int flags = 0;
+    int64_t *calls = nullptr, *fails = nullptr;
+    double *xin = nullptr, *uop = nullptr;
+    bool capturable() const { return (flags & CPK_OP_CAPTURABLE) != 0; }
+};
+// one call of fn on the context stream; a nonzero return throws CPK_ERR_CALLBACK naming the call
+inline void op_call(Ctx &c, const OpHook &op, const double *d_x, double *d_y, int64_t n) {
+    const int64_t k = ++*op.calls;
+    const int rc = op.fn(op.user, d_x, d_y, n, (void *)c.stream);
+    if (rc) {
+        ++*op.fails;
+        throw Error(CPK_ERR_CALLBACK, "the operator's callback returned " + std::to_string(rc) + " on call " +
+                                          std::to_string(k) + " of this operator");
+    }
+}
 // [x, y, stats, flag] = method(b, A, C, M, opts): d_b (n), d_xy (N), AC = blkdiag(A, C)
+// op (in all three entries below): A is op's callback; AC is then blkdiag(0, C), n empty rows
+// above C's, and Arows is not read.  Single GPU; the callers refuse the rest.
 void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, Precond &M, const cpk_opts *opts,
-                         double *d_xy, cpk_stats *stats);
+                         double *d_xy, cpk_stats *stats, const OpHook *op = nullptr);
 // reg_cpkrylov's shift + method + recovery (reg_cpkrylov.m:150-175): d_b (N), d_x (N)
 // The shift's products: rows < n of Arows*xy0 (= A*xy0(1:n)) and of Btrows*xy0 restricted to
 // columns >= bt_colmin (= B'*xy0(n+1:N)).
 void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, const DMat &Arows, const DMat &Btrows,
-                      int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
+                      int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats,
+                      const OpHook *op = nullptr);
 int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
+                     double *d_b1, double *d_xy0);
+// the same with A*xy0(1:n) made by one direct call of op's callback on xy0 and a buffer of this call
+int reg_shift_device(Ctx &c, const double *d_b, const OpHook &op, const DMat &Btrows, int64_t bt_colmin, Precond &M,
                      double *d_b1, double *d_xy0);
 // x = x0 + dx (the Recover functor of the shift's recovery; d_x may be d_x0), on the context stream
 void launch_recover(Ctx &c, int64_t N, const double *d_x0, const double *d_dx, double *d_x);
@@ -40,5 +69,8 @@ void debug_dot(Ctx &c, int kind, int64_t n, int nv, const double *d_A, int64_t l
                int grid, double *d_out);
 void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, double *d_out);
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out);
-double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts);
+// op: AC is blkdiag(0, C); the product's model adds the gather and the epilogue's read of fn's
+// output (24 n), cpminres runs unfused, and fn's own traffic is unknown and not counted
+double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts,
+                    const OpHook *op = nullptr);
 }  // namespace cpk

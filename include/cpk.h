@@ -38,7 +38,8 @@ typedef enum {
                                engine option pivot_min = 0 (the default), a zero one; a finished
                                factor's signs are in cpk_pc_factor_report, never an error */
     CPK_ERR_NOMEM = 7,
-    CPK_ERR_UNSUPPORTED = 8
+    CPK_ERR_UNSUPPORTED = 8,
+    CPK_ERR_CALLBACK = 9    /* the callback of an operator-valued A (cpk_op) returned nonzero */
 } cpk_status;
 
 /* Method ids: the function handles @cpcg, @cpcglanczos, @cpminres, @cpsymmlq, @cpgmres,
@@ -177,6 +178,12 @@ int cpk_mat_create_csr(cpk_ctx ctx, int64_t nrows, int64_t ncols, const int64_t 
 int cpk_mat_destroy(cpk_mat A);
 /* y = A*x on the device (host vectors in/out); replaces MATLAB sparse mtimes A*v. */
 int cpk_mat_spmv(cpk_mat A, const double *x, double *y);
+/* The same on device vectors: the product is enqueued on the context stream and nothing is waited
+ * for.  The same kernel on the same row blocks as cpk_mat_spmv, so the same bits.  Legal while
+ * the context stream is capturing, once the handle has its device copy: the first device use of a
+ * handle uploads it, so make one call (or any solve with the handle) before relying on that.  This
+ * is how a C caller writes a cpk_op callback out of the library's own SpMV. */
+int cpk_mat_spmv_device(cpk_mat A, const double *d_x, double *d_y);
 /* New values with the same sparsity, written into the handle (an interior-point outer iteration:
  * reg_cpkrylov.m:131 rebuilds opLDL2 from new values once per outer iteration).  val holds the
  * values in the order of the creating call's value array -- pr of cpk_mat_create_csc, val of
@@ -408,6 +415,65 @@ int cpk_reg_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_mat B
 /* reg_cpkrylov's shift + method + recovery with an existing M, device-resident b and x (N). */
 int cpk_reg_solve_device(cpk_ctx ctx, int method, const double *d_b, cpk_mat A, cpk_mat B, cpk_mat C,
                          cpk_pc M, const cpk_opts *opts, double *d_x, cpk_stats *stats);
+
+/* ---- the operator-valued A: the (1,1) block as a device callback ---------------------------- */
+/* reg_cpkrylov.m:40 and the header of every kernel (cpcg.m:44, cpminres.m:40, ...): A may be a
+ * matrix or a linear operator; only B, C and G must be matrices, since only they are factorized.
+ * A cpk_op is that operator: y(0:n) = A*x(0:n) on device memory, all work enqueued on `stream`
+ * (the context's hipStream_t).  Returns 0, or nonzero to abort the solve.
+ *
+ * The contract of fn:
+ *  - fn writes y[0:n) and touches nothing else.  In the per-iteration product x and y are two
+ *    buffers of the cached solver whose addresses stay fixed for that solver's life (the solver
+ *    copies the current Krylov vector into x first); the one product of reg_cpkrylov's shift and
+ *    cpk_op_apply_device pass the buffers of that call.
+ *  - A capturable op (CPK_OP_CAPTURABLE) may be called while the stream is capturing.  It must
+ *    only enqueue on `stream`: no synchronisation, no allocation, no other stream.  What it
+ *    enqueues may depend only on its arguments and on device memory contents, never on host state
+ *    at call time: fn is then called at capture time, once per captured iteration, and replays of
+ *    the graph do not call it.  The iterations run in the usual captured batches.
+ *  - A non-capturable op (the default) is called eagerly, once per product, and may do anything
+ *    on `stream` (a torch computation, its own synchronisation).  Its solver runs batches of one
+ *    iteration without graphs, so fn is never called for an iteration that has already stopped
+ *    and cpk_op_get_info's call count is exact: one per iteration, one for cpsymmlq's pre-step,
+ *    one per cpgmres restart, one for reg_cpkrylov's shift when b(n+1:N) is not zero.
+ *  - A nonzero return aborts the solve with CPK_ERR_CALLBACK; the message names the call count.
+ *    An open capture is ended and its graph discarded before the error propagates.  The outputs
+ *    are unspecified; every handle stays usable.
+ *  - A's symmetry is the caller's responsibility, as it is in the reference.
+ * An operator solve of cpminres runs the unfused update (engine option no_minres_fuse's sequence:
+ * the same bits).  u = fn's output bit for bit; t = C*q row sums in column order from 0.0 as in
+ * the matrix path; <u, v> and <t, q> are fixed-order sums, deterministic per build and device,
+ * and the correctly rounded exact sums under engine option exact_dots.
+ * stats->bytes_moved counts 12 nnz(C) + 4 (N+1) + 16 N + 24 n for the product (the 24 n: the copy
+ * of the Krylov vector to fn's input and the read of fn's output); fn's own traffic is unknown and
+ * NOT counted.
+ * Block solves, cpk_kkt and distributed contexts stay matrix-only.  THE OP MUST OUTLIVE THE
+ * PRECONDITIONERS IT WAS SOLVED WITH, OR THEIR LAST USE. */
+typedef int (*cpk_op_fn)(void *user, const double *d_x, double *d_y, int64_t n, void *stream);
+typedef struct cpk_op_s *cpk_op;
+#define CPK_OP_CAPTURABLE 1
+/* n >= 0 (CPK_ERR_DIM); flags: 0 or CPK_OP_CAPTURABLE (CPK_ERR_ARGS otherwise).  A NULL fn makes a
+ * handle that every solve and cpk_op_apply_device refuse (CPK_ERR_ARGS). */
+int cpk_op_create(cpk_ctx ctx, int64_t n, cpk_op_fn fn, void *user, int flags, cpk_op *out);
+int cpk_op_destroy(cpk_op A);
+/* info: n, flags, calls of fn so far, calls that returned nonzero */
+int cpk_op_get_info(cpk_op A, int64_t info[4]);
+/* one call of fn on the context stream (d_x, d_y: n values each); nothing is waited for */
+int cpk_op_apply_device(cpk_op A, const double *d_x, double *d_y);
+/* cpk_method_solve / cpk_method_solve_device with the operator A.  Refused before anything is
+ * written: a distributed context or preconditioner (CPK_ERR_UNSUPPORTED), an n that differs from
+ * M's or a C that does not fit (CPK_ERR_DIM), a NULL fn or handle (CPK_ERR_ARGS). */
+int cpk_method_solve_op(cpk_ctx ctx, int method, const double *b, cpk_op A, cpk_mat C, cpk_pc M, const cpk_opts *opts,
+                        double *x, double *y, cpk_stats *stats);
+int cpk_method_solve_op_device(cpk_ctx ctx, int method, const double *d_b, cpk_op A, cpk_mat C, cpk_pc M,
+                               const cpk_opts *opts, double *d_xy, cpk_stats *stats);
+/* reg_cpkrylov's shift + method + recovery with the operator A and an existing M (as
+ * cpk_reg_solve_device): host b and x (N), or device-resident ones.  The same refusals. */
+int cpk_reg_solve_op(cpk_ctx ctx, int method, const double *b, cpk_op A, cpk_mat B, cpk_mat C, cpk_pc M,
+                     const cpk_opts *opts, double *x, cpk_stats *stats);
+int cpk_reg_solve_op_device(cpk_ctx ctx, int method, const double *d_b, cpk_op A, cpk_mat B, cpk_mat C, cpk_pc M,
+                            const cpk_opts *opts, double *d_x, cpk_stats *stats);
 
 /* ---- the saddle-point operator itself: product, true residual, verified solve ------------ */
 /* K = [A B'; B -C], the matrix of the system reg_cpkrylov solves (reg_cpkrylov.m:1-40): A, B, C
