@@ -80,6 +80,9 @@ _SIGS = {
     "cpk_mat_spmv_device": ([vp, vp, vp], C.c_int),
     "cpk_mat_set_values": ([vp, P(C.c_double), C.c_int64], C.c_int),
     "cpk_mat_set_values_device": ([vp, vp, C.c_int64], C.c_int),
+    "cpk_mat_sample_outer": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, C.c_double,
+                              P(C.c_double), C.c_int64], C.c_int),
+    "cpk_mat_sample_outer_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_double, vp, C.c_int64], C.c_int),
     "cpk_mat_get_info": ([vp, P(C.c_int64)], C.c_int),
     "cpk_pc_create": ([vp, vp, vp, vp, P(C.c_double), P(vp)], C.c_int),
     "cpk_pc_create_hint": ([vp, vp, vp, vp, vp, P(C.c_double), P(vp)], C.c_int),
@@ -151,6 +154,11 @@ _SIGS = {
     "cpk_kkt_solve": ([vp, C.c_int, P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int, P(Stats), P(C.c_double)],
                       C.c_int),
     "cpk_kkt_solve_device": ([vp, C.c_int, vp, vp, P(Opts), vp, C.c_int, P(Stats), P(C.c_double)], C.c_int),
+    "cpk_kkt_adjoint": ([vp, vp, C.c_int, P(C.c_double), P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int,
+                         P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(Stats),
+                         P(C.c_double)], C.c_int),
+    "cpk_kkt_adjoint_device": ([vp, vp, C.c_int, vp, vp, vp, P(Opts), vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp,
+                                C.c_int64, P(Stats), P(C.c_double)], C.c_int),
     "cpk_method_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, vp, vp, P(Opts), P(C.c_double),
                                 C.c_int64, P(C.c_double), C.c_int64, P(Stats), P(C.c_int)], C.c_int),
     "cpk_method_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, P(Opts), vp, C.c_int64,

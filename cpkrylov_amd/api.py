@@ -231,6 +231,39 @@ class Matrix:
         check(lib.cpk_mat_set_values_device(self.h, C.c_void_p(int(ptr) if ptr else None), int(count)))
         self._val = None  # this object's host values are no longer the matrix's
 
+    def sample_outer(self, U, V, alpha=1.0, out=None):
+        """g = alpha * (u_0 v_0' + ... + u_{k-1} v_{k-1}') sampled on this matrix's sparsity, in the
+        order `set_values` takes values in (cpk_mat_sample_outer[_device]): the transpose of
+        `set_values`, a gradient with respect to those values.  Each entry's sum starts at 0.0 and
+        adds the separately rounded products in column order, alpha last; the matrix's values are
+        not read.  U (nrows x k) and V (ncols x k) are NumPy arrays (a vector is one column), and
+        the result is a new array or `out`; or both are device tensors (float64, contiguous, one
+        column after the other, so a (k, nrows) row-major tensor is the block) and the result goes
+        to the device tensor passed as out=, complete when the call returns."""
+        count = self.info()["entries"]
+        if _is_device(U) or _is_device(V):
+            if not (_is_device(U) and _is_device(V) and out is not None and _is_device(out)):
+                raise CpkError(_lib.CPK_ERR_ARGS, "sample_outer on device operands: U, V and out= are device tensors")
+            up, k, ldu = _device_operand(U, "U", self.shape[0])
+            vp, kv, ldv = _device_operand(V, "V", self.shape[1])
+            op, _, _ = _device_operand(out, "out", count)
+            if kv != k:
+                raise CpkError(_lib.CPK_ERR_DIM, "U and V must have the same number of columns")
+            check(lib.cpk_mat_sample_outer_device(self.h, k, up, ldu, vp, ldv, float(alpha), op, int(out.numel())))
+            check(lib.cpk_ctx_synchronize(self.ctx.h))
+            return out
+        U, V = (np.asarray(a, dtype=np.float64) for a in (U, V))
+        U, V = (np.asfortranarray(a.reshape(a.shape[0], -1) if a.ndim else a.reshape(1, 1)) for a in (U, V))
+        if U.shape[0] != self.shape[0] or V.shape[0] != self.shape[1] or U.shape[1] != V.shape[1]:
+            raise CpkError(_lib.CPK_ERR_DIM, "sample_outer: U is nrows x k and V is ncols x k")
+        if out is None:
+            out = np.zeros(count)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous):
+            raise CpkError(_lib.CPK_ERR_ARGS, "sample_outer: out is a contiguous float64 array")
+        check(lib.cpk_mat_sample_outer(self.h, U.shape[1], _dptr(U), max(self.shape[0], 1), _dptr(V), max(self.shape[1], 1),
+                                       float(alpha), _dptr(out) if out.size else None, out.size))
+        return out
+
     def info(self):
         """Diagnostic (cpk_mat_get_info): sizes, the values generation (0 at creation, +1 per
         successful set_values), whether a device copy exists, and the Krylov operators
@@ -1230,6 +1263,95 @@ class KKT:
         stats["true_resid0"] = _norms_dict(res[:4], True)
         stats["true_resid"] = _norms_dict(res[4:], True)
         return x, stats, flag
+
+    def adjoint(self, method, x, gx, M, opts=None, KT=None, lam0=None, out=None):
+        """The adjoint of `solve` (cpk_kkt_adjoint): with x = K \\ b and gx = dL/dx, returns
+        dict(db, dA, dB, dC, stats, flag) where db = lambda = K' \\ gx = dL/db and dA, dB, dC are
+        dL/d(values) of K's A, B and C on their own sparsity, each in the order its handle's
+        `set_values` takes values in: -lambda_x x_x', -(lambda_y x_x' + x_y lambda_x') and
+        +lambda_y x_y' sampled there (Matrix.sample_outer).  lambda is solved by
+        `(KT or self).solve(method, gx, M, opts, x0=lam0)`: stats and flag are that solve's, and
+        with lam0 (usually the previous outer iteration's lambda) its stop test runs on the
+        correction system.  KT is the KKT of the transposed system, KKT(A.T, B, C); without it the
+        caller asserts that A is symmetric, which is not checked.  One right-hand side.
+
+        Operands as for `solve`.  Host arrays: `out` may be a dict holding NumPy arrays for any
+        of "db", "dA", "dB", "dC" to be filled in place.  Device tensors (x and gx): out= is a dict
+        of device tensors, "db" required (lam0, if given, is out["db"] itself, updated in place)
+        and "dA", "dB", "dC" each optional -- a gradient that is absent is not formed.  A stop
+        inside the driver raises its own error, carrying `partial` = (lambda as far as the driver
+        wrote it, the eight sums); the gradient arrays are then untouched."""
+        name = getattr(method, "_cpk_method", method)
+        if name not in _lib.METHODS:
+            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+        if any(isinstance(v, Operator) for v in (x, gx, M, KT, lam0)):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.adjoint is matrix-only: an Operator has no entries to take a gradient on")
+        if not isinstance(M, opLDL2):
+            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        if KT is not None and not isinstance(KT, KKT):
+            raise CpkError(_lib.CPK_ERR_ARGS, "KT must be a KKT operator (of A.T, B, C)")
+        out = dict(out or {})
+        if set(out) - {"db", "dA", "dB", "dC"}:
+            raise CpkError(_lib.CPK_ERR_ARGS, "adjoint: out= holds db, dA, dB, dC")
+        st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
+        res = np.zeros(8)
+        counts = [h.info()["entries"] for h in (self.A, self.B, self.C)]
+        kth = KT.h if KT is not None else None
+        if _is_device(x) or _is_device(gx):
+            if not (_is_device(x) and _is_device(gx) and _is_device(out.get("db"))):
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint on device operands: x, gx and out['db'] are device tensors")
+            if lam0 is not None and lam0 is not out["db"]:
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint on device operands: lam0 is out['db'] itself (updated in place)")
+            ptrs = []
+            for v, what in ((x, "x"), (gx, "gx"), (out["db"], "out['db']")):
+                p, k, _ = _device_operand(v, what, self.N)
+                if k != 1:
+                    raise CpkError(_lib.CPK_ERR_DIM, "adjoint takes one right-hand side of N entries")
+                ptrs.append(p)
+            gp = []
+            for key, cnt in zip(("dA", "dB", "dC"), counts):
+                g = out.get(key)
+                if g is None:
+                    gp += [C.c_void_p(None), 0]
+                    continue
+                if not _is_device(g):
+                    raise CpkError(_lib.CPK_ERR_ARGS, f"adjoint on device operands: out[{key!r}] is a device tensor")
+                gp += [_device_operand(g, key, cnt)[0], int(g.numel())]
+            rc = lib.cpk_kkt_adjoint_device(self.h, kth, _lib.METHODS[name], ptrs[0], ptrs[1], M.h, C.byref(make_opts(opts)),
+                                            ptrs[2], int(lam0 is not None), *gp, C.byref(st), _dptr(res))
+            lam = out["db"]
+        else:
+            x, gx = (np.ascontiguousarray(np.asarray(v, dtype=np.float64)).ravel() for v in (x, gx))
+            if x.shape[0] != self.N or gx.shape[0] != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, "x and gx must have n+m entries")
+            for key, cnt in zip(("db", "dA", "dB", "dC"), [self.N] + counts):
+                g = out.setdefault(key, np.zeros(cnt))
+                if not (isinstance(g, np.ndarray) and g.dtype == np.float64 and g.flags.c_contiguous):
+                    raise CpkError(_lib.CPK_ERR_ARGS, f"adjoint: out[{key!r}] is a contiguous float64 array")
+            lam = out["db"]
+            if lam.size != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, "out['db'] must have n+m entries")
+            if lam0 is not None:
+                l0 = np.asarray(lam0, dtype=np.float64).ravel()
+                if l0.shape[0] != self.N:
+                    raise CpkError(_lib.CPK_ERR_DIM, "lam0 must have n+m entries")
+                lam[:] = l0
+            gp = []
+            for key in ("dA", "dB", "dC"):
+                gp += [_dptr(out[key]) if out[key].size else None, out[key].size]
+            rc = lib.cpk_kkt_adjoint(self.h, kth, _lib.METHODS[name], _dptr(x), _dptr(gx), M.h, C.byref(make_opts(opts)),
+                                     _dptr(lam), int(lam0 is not None), *gp, C.byref(st), _dptr(res))
+        if rc != _lib.CPK_OK:
+            try:
+                check(rc)
+            except CpkError as e:
+                e.partial = (lam, res.copy())
+                raise
+        stats, flag = _stats_from(name, st, hist, lq, qr)
+        stats["ptime"], stats["stime"] = st.ptime, st.stime
+        stats["true_resid0"] = _norms_dict(res[:4], True)
+        stats["true_resid"] = _norms_dict(res[4:], True)
+        return dict(db=lam, dA=out.get("dA"), dB=out.get("dB"), dC=out.get("dC"), stats=stats, flag=flag)
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -1,0 +1,175 @@
+// adjoint.hip -- a sum of outer products sampled on a matrix handle's sparsity and handed back in
+// the creating call's value order (cpk_mat_sample_outer[_device]): the value gradients of the
+// adjoint solve (cpk_kkt_adjoint, DESIGN.md "The adjoint solve").  For every stored entry
+// q = (i, j) of the canonical CSR
+//     g_q = alpha * (u_0[i]*v_0[j] + u_1[i]*v_1[j] + ... + u_{k-1}[i]*v_{k-1}[j]),
+// the sum from 0.0 over the separately rounded products in column order c = 0 ... k-1 (no FMA),
+// alpha applied last with one rounding.  g_q then goes back through the handle's value map
+// (host.hpp, ValueMap), the transpose of what set_values does with it: out[q] (identity),
+// out[perm[q]] (perm), or every source src[t], t in [sptr[q], sptr[q + 1]) (the summands of a
+// summed duplicate each have derivative 1).  Every caller entry is written exactly once: no
+// atomics, and the values of the matrix are never read.
+//
+// The walk is spmv_stream's (spmv.hpp): a workgroup owns row blocks of DMat::blk, whose entries
+// (<= kSpmvCap) are contiguous.  Its threads read their rows' pointers and write each row's local
+// index over the row's span of an LDS table, one 16-bit word per entry; then consecutive lanes take
+// consecutive entries, find the row in the table, gather u by row (neighbouring lanes share it) and
+// v by column, and store.  A row longer than kSpmvCap sits alone in its block and needs no table.
+// The index streams (columns, map) are read once per launch: non-temporal, so they leave the
+// caches to the gathered vectors.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "dev.hpp"
+#include "devutil.hpp"
+
+namespace cpk {
+
+namespace {
+
+enum { kMapIdentity = 0, kMapPerm = 1, kMapSum = 2 };
+
+// KC > 0: that many columns, unrolled (the adjoint's k = 1 and k = 2); KC == 0: k at run time
+template <int KC>
+__device__ __forceinline__ double outer_sum(int k, const double *__restrict__ U, int64_t ldu,
+                                            const double *__restrict__ V, int64_t ldv, int64_t row, int32_t c) {
+    double s = 0.0;
+    if constexpr (KC > 0) {
+        double u[KC], v[KC];
+#pragma unroll
+        for (int j = 0; j < KC; j++) u[j] = U[row + j * ldu], v[j] = V[c + j * ldv];
+#pragma unroll
+        for (int j = 0; j < KC; j++) s = s + u[j] * v[j];
+    } else {
+        for (int j = 0; j < k; j++) s = s + U[row + j * ldu] * V[c + j * ldv];
+    }
+    return s;
+}
+
+// m0: perm (kMapPerm) or sptr (kMapSum); m1: src (kMapSum)
+template <int MODE>
+__device__ __forceinline__ void map_store(const uint32_t *__restrict__ m0, const uint32_t *__restrict__ m1, uint32_t e,
+                                          double g, double *__restrict__ out) {
+    if constexpr (MODE == kMapIdentity) {
+        // a stream written once and read by nobody in this launch: non-temporal, as the index streams
+        // are read (k = 2 on A at S10: 88 -> 77 us; a scattered store gains nothing from it)
+        __builtin_nontemporal_store(g, out + e);
+    } else if constexpr (MODE == kMapPerm) {
+        out[__builtin_nontemporal_load(m0 + e)] = g;
+    } else {
+        const uint32_t t1 = __builtin_nontemporal_load(m0 + e + 1);
+        for (uint32_t t = __builtin_nontemporal_load(m0 + e); t < t1; t++) out[__builtin_nontemporal_load(m1 + t)] = g;
+    }
+}
+
+template <int KC, int MODE>
+__global__ __launch_bounds__(kBlock) void sample_outer_kernel(const uint32_t *__restrict__ ptr,
+                                                               const int32_t *__restrict__ col,
+                                                               const int32_t *__restrict__ blk, int64_t nblk, int k,
+                                                               const double *__restrict__ U, int64_t ldu,
+                                                               const double *__restrict__ V, int64_t ldv, double alpha,
+                                                               const uint32_t *__restrict__ m0,
+                                                               const uint32_t *__restrict__ m1,
+                                                               double *__restrict__ out) {
+    __shared__ uint16_t srow[kSpmvCap];  // entry of the block -> its row, local to the block
+    constexpr int EPT = kSpmvCap / kBlock, RPT = kSpmvMaxRows / kBlock;
+    const int tid = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
+        if (b != blockIdx.x) __syncthreads();  // srow[] of the previous block fully consumed
+        const int64_t r0 = blk[b], r1 = blk[b + 1];
+        const uint32_t e0 = ptr[r0], e1 = ptr[r1];
+        if (e1 == e0) continue;  // no entry (uniform over the workgroup); below, e1 - 1 and r1 - 1 exist
+        if (e1 - e0 <= (uint32_t)kSpmvCap) {
+            // every load is unconditional, on an index clamped into the block (a lane past the end
+            // repeats the block's last entry or row and stores nothing), so a thread's loads of one
+            // kind are all in flight at once: under `e < e1 ? load : 0` the compiler branched around
+            // each load and waited for it before the next
+            int32_t cc[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; j++) {
+                const uint32_t e = e0 + tid + j * kBlock;
+                cc[j] = __builtin_nontemporal_load(col + (e < e1 ? e : e1 - 1));
+            }
+            uint32_t pa[RPT], pb[RPT];
+#pragma unroll
+            for (int j = 0; j < RPT; j++) {
+                const int64_t r = r0 + tid + j * kBlock < r1 ? r0 + tid + j * kBlock : r1 - 1;
+                pa[j] = __builtin_nontemporal_load(ptr + r), pb[j] = __builtin_nontemporal_load(ptr + r + 1);
+            }
+#pragma unroll
+            for (int j = 0; j < RPT; j++)
+                if (r0 + tid + j * kBlock < r1)
+                    for (uint32_t q = pa[j] - e0; q < pb[j] - e0; q++) srow[q] = (uint16_t)(tid + j * kBlock);
+            __syncthreads();
+            double s[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; j++) {
+                const uint32_t q = tid + j * kBlock;
+                s[j] = outer_sum<KC>(k, U, ldu, V, ldv, r0 + srow[q < e1 - e0 ? q : e1 - e0 - 1], cc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < EPT; j++) {
+                const uint32_t e = e0 + tid + j * kBlock;
+                if (e < e1) map_store<MODE>(m0, m1, e, alpha * s[j], out);
+            }
+        } else {  // one long row (r1 == r0 + 1)
+            for (uint32_t e = e0 + tid; e < e1; e += kBlock) {
+                const double s = outer_sum<KC>(k, U, ldu, V, ldv, r0, __builtin_nontemporal_load(col + e));
+                map_store<MODE>(m0, m1, e, alpha * s, out);
+            }
+        }
+    }
+}
+
+// the workgroups resident at once (as spmv_grid sizes the SpMV's launch): each walks every
+// grid-th row block
+template <int KC, int MODE>
+unsigned sample_grid(int64_t nblk) {
+    static const int64_t resident = [] {
+        int occ = 0, dev = 0, cus = 256;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)sample_outer_kernel<KC, MODE>, kBlock, 0) !=
+                hipSuccess ||
+            occ < 1)
+            occ = 1;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return (int64_t)occ * cus;
+    }();
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(nblk, resident));
+}
+
+template <int KC, int MODE>
+void sample_launch(Ctx &c, const DMat &A, int k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                   const uint32_t *m0, const uint32_t *m1, double *out) {
+    hipLaunchKernelGGL((sample_outer_kernel<KC, MODE>), dim3(sample_grid<KC, MODE>(A.nblk)), dim3(kBlock), 0, c.stream,
+                       A.ptr.p, A.col.p, A.blk.p, A.nblk, k, U, ldu, V, ldv, alpha, m0, m1, out);
+    CPK_HIP(hipGetLastError());
+}
+
+template <int MODE>
+void sample_launch_k(Ctx &c, const DMat &A, int k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                     const uint32_t *m0, const uint32_t *m1, double *out) {
+    if (k == 1) sample_launch<1, MODE>(c, A, k, U, ldu, V, ldv, alpha, m0, m1, out);
+    else if (k == 2) sample_launch<2, MODE>(c, A, k, U, ldu, V, ldv, alpha, m0, m1, out);
+    else sample_launch<0, MODE>(c, A, k, U, ldu, V, ldv, alpha, m0, m1, out);
+}
+
+}  // namespace
+
+void launch_sample_outer(Ctx &c, const DMat &A, const ValueMap &vm, const DValueMap &dm, int64_t k, const double *U,
+                         int64_t ldu, const double *V, int64_t ldv, double alpha, double *out) {
+    if (A.nnz <= 0) return;  // no stored entry, so no entry of the creating call either
+    if (k > INT32_MAX) throw Error(CPK_ERR_DIM, "sample_outer: k out of range");
+    // the maps hold one entry per stored entry (perm: nnz, sptr: nnz + 1); every destination index
+    // is below vm.count, the length the caller's array was checked against
+    const bool sum = !vm.identity && !vm.sptr.empty();
+    if (!vm.identity &&
+        (!dm.ready || (sum ? dm.sptr.n != (size_t)A.nnz + 1 || dm.src.n != (size_t)vm.count : dm.perm.n != (size_t)A.nnz)))
+        throw Error(CPK_ERR_ARGS, "sample_outer: the device value map does not match the matrix");
+    if (vm.identity) sample_launch_k<kMapIdentity>(c, A, (int)k, U, ldu, V, ldv, alpha, nullptr, nullptr, out);
+    else if (sum) sample_launch_k<kMapSum>(c, A, (int)k, U, ldu, V, ldv, alpha, dm.sptr.p, dm.src.p, out);
+    else sample_launch_k<kMapPerm>(c, A, (int)k, U, ldu, V, ldv, alpha, dm.perm.p, nullptr, out);
+}
+
+}  // namespace cpk

@@ -197,6 +197,7 @@ struct cpk_kkt_s {
     int route = 0;
     int64_t panels = 0;
     DBuf<double> Tp;
+    DBuf<double> ws;  // cpk_kkt_solve's vectors (kkt_solve_core), allocated by the first solve and kept
     // the operator on the handles' current values: a device gather where a values generation
     // moved (the value array keeps its address; nothing goes through the host)
     const DMat &current() {
@@ -535,6 +536,48 @@ int cpk_mat_set_values_device(cpk_mat A, const double *d_val, int64_t count) {
     CPK_HIP(hipStreamSynchronize(c.stream));  // d_val is the caller's again
     A->h_stale = d.nnz > 0;
     A->vgen++;
+    API_END
+}
+
+// the checks of both sampled outer products, in set_values_device's order; nothing is touched
+// before they pass
+static void check_sample_outer(cpk_mat A, int64_t k, const double *U, int64_t ldu, const double *V, int64_t ldv,
+                               const double *out, int64_t count) {
+    need(A != nullptr, "NULL matrix handle");
+    need(out != nullptr || count <= 0, "NULL output array");
+    need(k <= 0 || ((U != nullptr || A->h.nrows == 0) && (V != nullptr || A->h.ncols == 0)), "NULL operand");
+    if (count != A->vm.count) throw Error(CPK_ERR_DIM, "sample_outer: count differs from the creating call's entry count");
+    if (k < 0 || (k > 0 && (ldu < A->h.nrows || ldv < A->h.ncols)))
+        throw Error(CPK_ERR_DIM, "sample_outer: k >= 0, ldu >= nrows and ldv >= ncols required");
+    if (!A->ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
+    if (A->ctx->c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "sample_outer: single-GPU only");
+}
+
+int cpk_mat_sample_outer_device(cpk_mat A, int64_t k, const double *d_U, int64_t ldu, const double *d_V, int64_t ldv,
+                                double alpha, double *d_out, int64_t count) {
+    API_BEGIN
+    check_sample_outer(A, k, d_U, ldu, d_V, ldv, d_out, count);
+    const DMat &d = A->dev();
+    upload_value_map(A->vm, A->dvm);
+    launch_sample_outer(A->ctx->c, d, A->vm, A->dvm, k, d_U, ldu, d_V, ldv, alpha, d_out);
+    API_END
+}
+
+int cpk_mat_sample_outer(cpk_mat A, int64_t k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                         double *out, int64_t count) {
+    API_BEGIN
+    check_sample_outer(A, k, U, ldu, V, ldv, out, count);
+    if (count == 0) return CPK_OK;
+    Ctx &c = A->ctx->c;
+    const DMat &d = A->dev();
+    upload_value_map(A->vm, A->dvm);
+    HostBlock dU(A->h.nrows, k), dV(A->h.ncols, k);
+    if (k) dU.up(U, ldu), dV.up(V, ldv);
+    DBuf<double> dg;
+    dg.alloc((size_t)count);
+    launch_sample_outer(c, d, A->vm, A->dvm, k, dU.d.p, dU.ld(), dV.d.p, dV.ld(), alpha, dg.p);
+    CPK_HIP(hipMemcpyAsync(out, dg.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
     API_END
 }
 
@@ -1239,6 +1282,11 @@ static void kkt_solve_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, c
     const DMat &AC = A->krylov_op(C, p);
     const ShiftOps so = shift_ops(A, C, p);
     double *dn = K->norms.p;
+    // the driver's vectors live in K, so every call hands the method the same addresses and finds
+    // the solver M cached under them (solver_key): [shift's three; warm residual; warm correction]
+    const size_t wsn = reg_solve_ws(N, K->n), part = reg_solve_ws_part(N);
+    if (K->ws.n < wsn + 2 * part) K->ws.alloc(wsn + 2 * part);
+    double *ws = K->ws.p;
     if (stats) stats->ptime = p.ptime;  // also where the driver stops with its error
     auto finish = [&] {
         launch_kkt_resid(c, Kd, K->n, d_x, d_b, nullptr, dn + 4);
@@ -1250,23 +1298,22 @@ static void kkt_solve_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, c
         if (N) CPK_HIP(hipMemsetAsync(d_x, 0, N * sizeof(double), c.stream));
         launch_kkt_sums(c, Kd, K->n, d_b, d_b, dn);
         try {
-            reg_solve_device(c, method, d_b, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_x, stats);
+            reg_solve_device(c, method, d_b, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_x, stats, nullptr, ws);
         } catch (...) {
             finish();
             throw;
         }
     } else {
-        DBuf<double> r, dx;
-        r.alloc((size_t)std::max<int64_t>(N, 1)), dx.alloc((size_t)std::max<int64_t>(N, 1));
-        dx.zero(c.stream);
-        launch_kkt_resid(c, Kd, K->n, d_x, d_b, r.p, dn);
+        double *r = ws + wsn, *dx = r + part;
+        CPK_HIP(hipMemsetAsync(dx, 0, (size_t)std::max<int64_t>(N, 1) * sizeof(double), c.stream));
+        launch_kkt_resid(c, Kd, K->n, d_x, d_b, r, dn);
         std::exception_ptr err;
         try {
-            reg_solve_device(c, method, r.p, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dx.p, stats);
+            reg_solve_device(c, method, r, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dx, stats, nullptr, ws);
         } catch (...) {
             err = std::current_exception();
         }
-        launch_recover(c, N, d_x, dx.p, d_x);  // x0 plus whatever the driver wrote
+        launch_recover(c, N, d_x, dx, d_x);  // x0 plus whatever the driver wrote
         if (err) {
             finish();
             std::rethrow_exception(err);
@@ -1300,6 +1347,88 @@ int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_op
         err = std::current_exception();
     }
     if (N) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (err) std::rethrow_exception(err);
+    API_END
+}
+
+// ---- the adjoint of the verified solve: lambda = K' \ gx, then the value gradients sampled on K's
+// own handles (adjoint.hip).  The checks first, so a refusal writes nothing; a stop inside the driver
+// leaves through kkt_solve_core's exception before any gradient pass is enqueued.
+static void check_kkt_adjoint(cpk_kkt K, cpk_kkt KT, cpk_pc M, const double *x, const double *gx, const double *lam,
+                              const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC, int64_t cC) {
+    need(K && M && ((x && gx && lam) || !(K->n + K->m)), "NULL argument");
+    need(!KT || (KT->ctx == K->ctx && KT->n == K->n && KT->m == K->m), "kkt_adjoint: KT's dimensions differ from K's");
+    const cpk_mat_s *h[3] = {K->A, K->B, K->C};
+    const double *g[3] = {gA, gB, gC};
+    const int64_t cnt[3] = {cA, cB, cC};
+    for (int i = 0; i < 3; i++)
+        if (g[i] && cnt[i] != h[i]->vm.count)
+            throw Error(CPK_ERR_DIM, "kkt_adjoint: a gradient's count differs from its handle's creating call's entry count");
+}
+
+// d_x, d_lam: N device values each; d_g*: device arrays of the handles' entry counts (or null)
+static void kkt_adjoint_core(cpk_kkt K, cpk_kkt KT, int method, const double *d_x, const double *d_gx, cpk_pc M,
+                             const cpk_opts *opts, double *d_lam, int warm, double *d_gA, double *d_gB, double *d_gC,
+                             cpk_stats *stats, double *res) {
+    kkt_solve_core(KT ? KT : K, method, d_gx, M, opts, d_lam, warm, stats, res);
+    if (!d_gA && !d_gB && !d_gC) return;
+    Ctx &c = K->ctx->c;
+    const int64_t n = K->n;
+    // gB's two terms pair x with lambda both ways, U = [lambda_y, x_y] and V = [x_x, lambda_x]: the
+    // second column of each lies in the other vector, so the kernel's column stride is the distance
+    // between the two vectors in doubles, positive for one operand and negative for the other (two
+    // device arrays of doubles; the launcher takes any stride, the public entries only ld >= rows)
+    const int64_t lam_to_x = ((int64_t)(intptr_t)d_x - (int64_t)(intptr_t)d_lam) / (int64_t)sizeof(double);
+    auto pass = [&](cpk_mat_s *H, int64_t k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                    double *out) {
+        if (!out) return;
+        const DMat &d = H->dev();
+        upload_value_map(H->vm, H->dvm);
+        launch_sample_outer(c, d, H->vm, H->dvm, k, U, ldu, V, ldv, alpha, out);
+    };
+    pass(K->A, 1, d_lam, 0, d_x, 0, -1.0, d_gA);                          // -lambda_x * x_x'
+    pass(K->B, 2, d_lam + n, lam_to_x, d_x, -lam_to_x, -1.0, d_gB);       // -(lambda_y * x_x' + x_y * lambda_x')
+    pass(K->C, 1, d_lam + n, 0, d_x + n, 0, 1.0, d_gC);                   // +lambda_y * x_y' (K holds -C)
+}
+
+int cpk_kkt_adjoint_device(cpk_kkt K, cpk_kkt KT, int method, const double *d_x, const double *d_gx, cpk_pc M,
+                           const cpk_opts *opts, double *d_lam, int warm, double *d_gA, int64_t cA, double *d_gB, int64_t cB,
+                           double *d_gC, int64_t cC, cpk_stats *stats, double *res) {
+    API_BEGIN
+    check_kkt_adjoint(K, KT, M, d_x, d_gx, d_lam, d_gA, cA, d_gB, cB, d_gC, cC);
+    kkt_adjoint_core(K, KT, method, d_x, d_gx, M, opts, d_lam, warm, d_gA, d_gB, d_gC, stats, res);
+    CPK_HIP(hipStreamSynchronize(K->ctx->c.stream));  // the gradients are the caller's
+    API_END
+}
+
+int cpk_kkt_adjoint(cpk_kkt K, cpk_kkt KT, int method, const double *x, const double *gx, cpk_pc M, const cpk_opts *opts,
+                    double *lam, int warm, double *gA, int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC,
+                    cpk_stats *stats, double *res) {
+    API_BEGIN
+    check_kkt_adjoint(K, KT, M, x, gx, lam, gA, cA, gB, cB, gC, cC);
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    DBuf<double> dx, dgx, dlam, dg[3];
+    h2d(dx, x, (size_t)N), h2d(dgx, gx, (size_t)N);
+    if (warm) h2d(dlam, lam, (size_t)N);
+    else dlam.alloc((size_t)std::max<int64_t>(N, 1));
+    double *g[3] = {gA, gB, gC};
+    const int64_t cnt[3] = {cA, cB, cC};
+    for (int i = 0; i < 3; i++)
+        if (g[i]) dg[i].alloc((size_t)std::max<int64_t>(cnt[i], 1));
+    std::exception_ptr err;
+    try {
+        kkt_adjoint_core(K, KT, method, dx.p, dgx.p, M, opts, dlam.p, warm, g[0] ? dg[0].p : nullptr,
+                         g[1] ? dg[1].p : nullptr, g[2] ? dg[2].p : nullptr, stats, res);
+    } catch (...) {
+        err = std::current_exception();
+    }
+    if (N) CPK_HIP(hipMemcpyAsync(lam, dlam.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    if (!err)
+        for (int i = 0; i < 3; i++)
+            if (g[i] && cnt[i])
+                CPK_HIP(hipMemcpyAsync(g[i], dg[i].p, (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     CPK_HIP(hipStreamSynchronize(c.stream));
     if (err) std::rethrow_exception(err);
     API_END

@@ -232,6 +232,14 @@ void upload_value_map(const ValueMap &vm, DValueMap &dm);
 // out (nnz stored entries) from the creating call's value order `in`, both on the device, on the
 // context stream (setvalues.hip); nothing is waited for
 void launch_set_values(Ctx &c, const ValueMap &vm, const DValueMap &dm, int64_t nnz, const double *in, double *out);
+// the transpose of that pass (adjoint.hip): g_q = alpha * sum_{c < k} U(i, c) * V(j, c) for every
+// stored entry q = (i, j) of A, the sum from 0.0 in column order without FMA, written to the
+// creating call's entries that q came from (out: vm.count values, each written once).  U (nrows x k)
+// and V (ncols x k) column-major, column c at U + c * ldu and V + c * ldv (any stride in doubles,
+// also a negative one: the adjoint's columns lie in two vectors); A's values are not read.  All on
+// the device, on the context stream; nothing is waited for
+void launch_sample_outer(Ctx &c, const DMat &A, const ValueMap &vm, const DValueMap &dm, int64_t k, const double *U,
+                         int64_t ldu, const double *V, int64_t ldv, double alpha, double *out);
 // The saddle-point operator K = [A B'; B -C] (kkt.hip; K in assemble_kp's entry order, n = size of
 // the (1,1) block), all on the context stream, nothing waited for:
 // out[q] = the entry src[q] of [va (na); vb (nb); vc], the vc entries negated

@@ -2170,6 +2170,12 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
     case CPK_GMRES: s.gmres(d_b, d_xy, stats); break;
     case CPK_DQGMRES: s.dqgmres(d_b, d_xy, stats); break;
     }
+    // keyed as the NEXT call will ask for it: a new solver's first run may have grown the context's
+    // reduction workspace before it captured its graphs (setup_state; cpgmres and cpdqgmres take one
+    // partial per basis vector), and that address is part of the key -- under the key of the lookup
+    // the solver, and the graphs it has just captured, would never be found again
+    for (auto &e : M.solvers)
+        if (e.second.get() == &s) e.first = solver_key(c, M, AC, method, opts, d_b, d_xy, op);
     CPK_HIP(hipEventRecord(c.ev1, c.stream));
     CPK_HIP(hipEventSynchronize(c.ev1));
     check_chain(M.dF);
@@ -2232,15 +2238,23 @@ int reg_shift_device(Ctx &c, const double *d_b, const OpHook &op, const DMat &Bt
 
 void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, const DMat &Arows, const DMat &Btrows,
                       int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats,
-                      const OpHook *op) {
+                      const OpHook *op, double *ws) {
     const int64_t n = M.n, N = M.N;
     auto t0 = std::chrono::steady_clock::now();
-    DBuf<double> xy0, b1, dxy;
-    xy0.alloc(std::max<int64_t>(N, 1)), b1.alloc(std::max<int64_t>(n, 1)), dxy.alloc(std::max<int64_t>(N, 1));
-    const int shift = op ? reg_shift_device(c, d_b, *op, Btrows, bt_colmin, M, b1.p, xy0.p)
-                         : reg_shift_device(c, d_b, Arows, Btrows, bt_colmin, M, b1.p, xy0.p);
-    method_solve_device(c, method, b1.p, AC, M, opts, shift ? dxy.p : d_x, stats, op);
-    if (shift) launch_ew(c, N, Recover{xy0.p, dxy.p, d_x});  // x = [xy0(1:n) + dx; xy0(n+1:N) + dy]
+    // the shift's vectors: this call's own, or the caller's ws (reg_solve_ws doubles), whose
+    // addresses stay from call to call -- they are part of the cached solver's key (solver_key)
+    DBuf<double> o_xy0, o_b1, o_dxy;
+    double *xy0, *b1, *dxy;
+    if (ws) {
+        xy0 = ws, dxy = ws + reg_solve_ws_part(N), b1 = dxy + reg_solve_ws_part(N);
+    } else {
+        o_xy0.alloc(std::max<int64_t>(N, 1)), o_b1.alloc(std::max<int64_t>(n, 1)), o_dxy.alloc(std::max<int64_t>(N, 1));
+        xy0 = o_xy0.p, b1 = o_b1.p, dxy = o_dxy.p;
+    }
+    const int shift = op ? reg_shift_device(c, d_b, *op, Btrows, bt_colmin, M, b1, xy0)
+                         : reg_shift_device(c, d_b, Arows, Btrows, bt_colmin, M, b1, xy0);
+    method_solve_device(c, method, b1, AC, M, opts, shift ? dxy : d_x, stats, op);
+    if (shift) launch_ew(c, N, Recover{xy0, dxy, d_x});  // x = [xy0(1:n) + dx; xy0(n+1:N) + dy]
     CPK_HIP(hipStreamSynchronize(c.stream));
     if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }

@@ -36,7 +36,13 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
 // columns >= bt_colmin (= B'*xy0(n+1:N)).
 void reg_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, const DMat &Arows, const DMat &Btrows,
                       int64_t bt_colmin, Precond &M, const cpk_opts *opts, double *d_x, cpk_stats *stats,
-                      const OpHook *op = nullptr);
+                      const OpHook *op = nullptr, double *ws = nullptr);
+// ws (optional): device memory for the shift's three vectors in place of the call's own allocations,
+// reg_solve_ws(N, n) doubles, each vector on a 256-byte boundary of it.  A caller that keeps it (K of
+// cpk_kkt_solve) hands the method the same addresses at every call, so the solver cached by M under
+// them, with its captured graphs, is found again
+inline size_t reg_solve_ws_part(int64_t len) { return ((size_t)std::max<int64_t>(len, 1) + 31) / 32 * 32; }
+inline size_t reg_solve_ws(int64_t N, int64_t n) { return 2 * reg_solve_ws_part(N) + reg_solve_ws_part(n); }
 int reg_shift_device(Ctx &c, const double *d_b, const DMat &Arows, const DMat &Btrows, int64_t bt_colmin, Precond &M,
                      double *d_b1, double *d_xy0);
 // the same with A*xy0(1:n) made by one direct call of op's callback on xy0 and a buffer of this call

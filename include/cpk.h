@@ -205,6 +205,25 @@ int cpk_mat_set_values(cpk_mat A, const double *val, int64_t count);
  * downloaded again when a host-side reader next needs it (cpk_pc_create, cpk_analyze, the first
  * blkdiag(A, C) of a pairing). */
 int cpk_mat_set_values_device(cpk_mat A, const double *d_val, int64_t count);
+/* A sum of k outer products sampled on A's sparsity, handed back in the creating call's value
+ * order: the transpose of cpk_mat_set_values (a gradient with respect to the values that call
+ * takes).  For every stored entry q = (i, j) of the canonical matrix
+ *     g_q = alpha * (U(i,0)*V(j,0) + U(i,1)*V(j,1) + ... + U(i,k-1)*V(j,k-1)),
+ * the sum from 0.0 over the separately rounded products in column order (no FMA), alpha applied
+ * last with one rounding; k == 0 gives alpha*0.0.  U is nrows x k and V is ncols x k, column-major
+ * with ldu >= nrows, ldv >= ncols.  out has count entries, count as for cpk_mat_set_values: entry e
+ * receives the g_q of the stored entry it went into, so the entries that were summed into one
+ * stored entry all receive that entry's g_q (the derivative of a sum with respect to each summand
+ * is 1).  Every entry of out is written exactly once, without atomics: the result is
+ * deterministic.  A's values are not read.  The work is done on the device in both variants.
+ * Refused before anything is written: a NULL handle, NULL out with count > 0, NULL U or V with
+ * k > 0 (CPK_ERR_ARGS); count differing from the creating call's, k < 0 or a short leading dimension
+ * (CPK_ERR_DIM); a host-only matrix (CPK_ERR_ARGS); a distributed context (CPK_ERR_UNSUPPORTED).
+ * _device: device arrays, enqueued on the context stream; nothing is waited for. */
+int cpk_mat_sample_outer(cpk_mat A, int64_t k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                         double *out, int64_t count);
+int cpk_mat_sample_outer_device(cpk_mat A, int64_t k, const double *d_U, int64_t ldu, const double *d_V, int64_t ldv,
+                                double alpha, double *d_out, int64_t count);
 /* Diagnostic: info[8] = {nrows, ncols, stored entries, entry count of the creating call, values
  * generation (0 at creation, +1 per successful set), device copy present, Krylov operators
  * cached on this handle, 0}. */
@@ -541,6 +560,30 @@ int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_op
                   cpk_stats *stats, double *res);
 int cpk_kkt_solve_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
                          cpk_stats *stats, double *res);
+/* The adjoint of that solve, one right-hand side: with x = K \ b and gx = dL/dx it returns
+ * lam = K' \ gx = dL/db and the gradients with respect to the values of K's own handles, each in
+ * its handle's creating call's value order (cpk_mat_sample_outer on that handle; x = [xx; xy],
+ * lam = [lx; ly]):
+ *     gA (cA entries) = -lx_i * xx_j                     on A's entries (i, j),
+ *     gB (cB entries) = -(ly_i * xx_j + xy_i * lx_j)     on B's, one term for each place B sits in K,
+ *     gC (cC entries) = +ly_i * xy_j                     on C's (K holds -C).
+ * gA, gB, gC may each be NULL; a count must be its handle's entry count (CPK_ERR_DIM).  G gets no
+ * gradient: the preconditioner does not change the solution.  Second derivatives are not formed.
+ * lam is solved by cpk_kkt_solve[_device](KT ? KT : K, method, gx, M, opts, lam, warm, stats, res):
+ * stats and res are that solve's, and warm != 0 takes lam as the start (usually the previous outer
+ * iteration's lam), with that call's stop test on the correction system.  KT is the operator of
+ * the transposed system, built on A', B, C; KT == NULL solves with K itself, BY WHICH THE CALLER
+ * ASSERTS THAT A IS SYMMETRIC: this is not checked.  A stop inside the driver is returned with the
+ * driver's own code and message; lam is then whatever the driver wrote, and no gradient array is
+ * touched.  Refusals, before anything is written: those of cpk_kkt_solve, and CPK_ERR_ARGS when KT
+ * is given and its context or dimensions differ from K's.  The call returns when the gradients are
+ * complete.  x, gx, lam: N entries; host arrays, or (_device) device arrays, gradients included. */
+int cpk_kkt_adjoint(cpk_kkt K, cpk_kkt KT, int method, const double *x, const double *gx, cpk_pc M, const cpk_opts *opts,
+                    double *lam, int warm, double *gA, int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC,
+                    cpk_stats *stats, double *res);
+int cpk_kkt_adjoint_device(cpk_kkt K, cpk_kkt KT, int method, const double *d_x, const double *d_gx, cpk_pc M,
+                           const cpk_opts *opts, double *d_lam, int warm, double *d_gA, int64_t cA, double *d_gB, int64_t cB,
+                           double *d_gC, int64_t cC, cpk_stats *stats, double *res);
 
 /* ---- a block of right-hand sides in lockstep (cpcg and cpminres) ------------------------ */
 /* [X(:,j), Y(:,j), stats(j), flag(j)] = method(B(:,j), A, C, M, opts) for j < k
