@@ -114,6 +114,7 @@ _SIGS = {
     "cpk_analysis_export": ([vp, P(C.c_int64), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_int32)],
                             C.c_int),
     "cpk_analysis_schedule": ([vp, P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int32)], C.c_int),
+    "cpk_analysis_round_caps": ([vp, P(C.c_int32), P(C.c_int32)], C.c_int),
     "cpk_analysis_plan": ([vp, vp, vp, C.c_int, C.c_int, P(vp)], C.c_int),
     "cpk_analysis_rowspan": ([vp, C.c_int64, C.c_int, C.c_int64, P(RowspanInfo), P(C.c_int64), P(C.c_int32),
                               P(C.c_double), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_uint64), P(C.c_int32),

@@ -714,6 +714,8 @@ def analyze(A, B, Cm, ctx=None, options=None):
         order = np.empty(N, np.int32)
         check(lib.cpk_analysis_schedule(h, None, rp.ctypes.data_as(_P(C.c_int64)), bl.ctypes.data_as(_P(C.c_int64)),
                                         lr.ctypes.data_as(_P(C.c_int64)), order.ctypes.data_as(_P(C.c_int32))))
+        rcap, rrows = np.empty(info["nrounds"], np.int32), np.empty(info["nrounds"], np.int32)
+        check(lib.cpk_analysis_round_caps(h, rcap.ctypes.data_as(_P(C.c_int32)), rrows.ctypes.data_as(_P(C.c_int32))))
         rep = _lib.FactorReport()
         check(lib.cpk_analysis_factor_report(h, C.byref(rep)))
         E = np.empty(N)
@@ -722,7 +724,7 @@ def analyze(A, B, Cm, ctx=None, options=None):
         lib.cpk_analysis_destroy(h)
     L = sp.csc_matrix((Lx[:nnz], Li[:nnz], Lp), shape=(N, N))
     return dict(info=info, L=L, D=D, perm=perm, round_ptr=rp, blk_lvl=bl, lvl_row=lr, order=order,
-                report=_report_dict(rep), E=E)
+                round_cap=rcap, round_rows=rrows, report=_report_dict(rep), E=E)
 
 
 _PLAN_F64 = {"fsub_Lx", "fsub_D", "extra_val", "tf_val", "tb_val", "DT", "kp_val", "ac_val", "ab_val"}

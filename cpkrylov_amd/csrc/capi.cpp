@@ -1779,6 +1779,18 @@ int cpk_analysis_schedule(cpk_analysis a, int64_t *nlevels, int64_t *round_ptr, 
     API_END
 }
 
+int cpk_analysis_round_caps(cpk_analysis a, int32_t *cap, int32_t *rows) {
+    API_BEGIN
+    need(a, "NULL argument");
+    const Schedule &s = a->an.S;
+    const SweepConfig &sw = a->an.sweep;
+    for (size_t r = 0; r + 1 < s.round_ptr.size(); r++) {
+        if (cap) cap[r] = r < s.round_cap.size() ? s.round_cap[r] : sw.cap[r == 0 ? 0 : 1];
+        if (rows) rows[r] = r < s.round_rows.size() ? s.round_rows[r] : sw.rows[r == 0 ? 0 : 1];
+    }
+    API_END
+}
+
 int cpk_analysis_rowspan(cpk_analysis a, int64_t block, int dir, int64_t cap_entries, cpk_rowspan_info *info,
                          int64_t *rowptr, int32_t *col, double *val, int32_t *dest, int32_t *step, int32_t *lead,
                          uint64_t *mask, int32_t *base, int32_t *first, int32_t *run0, uint8_t *tab) {

@@ -137,6 +137,11 @@ struct EngineOpts {
     bool no_chain = false;        // no_chain:           upper rounds one launch per round (not the sweep chain)
     bool no_bcast_analysis = false;  // no_bcast_analysis: every rank of a distributed preconditioner runs the global analysis
     int chain_wide = 256;         // chain_wide:         rounds of at most this many blocks join the sweep chain
+    int round_caps = 1;           // round_caps:         per-round block caps above round 1 (round_ladder): 0 uniform
+                                  //                     caps, 1 the ladder derived from the LDS limit where round 1
+                                  //                     is wider than the device holds at once, N > 1 every round
+                                  //                     above round 1 at N entries (tests); single GPU with the
+                                  //                     default sweep only
     bool dist_graph = true;       // dist_graph:         capture collectives in the graphs
     bool dist1 = false;           // dist1:              a 1-rank communicator runs the distributed path
                                   //                     (diagnostic; set before building operators)
@@ -163,6 +168,16 @@ void set_engine_option(EngineOpts &o, const std::string &name, const std::string
 std::string get_engine_option(const EngineOpts &o, const std::string &name, bool dist = false);
 // the sweep configuration a preconditioner of this path is built with
 SweepConfig effective_sweep(const EngineOpts &o, bool dist);
+// The LDS a block kernel's image may take: gfx950's 160 KB per workgroup less the kernels' static
+// words (the chain's epoch), and the CUs a round's blocks are resident on
+constexpr size_t kSweepLdsLimit = 160 * 1024 - 64;
+constexpr int64_t kSweepCus = 256;
+// the per-round caps a preconditioner of this path is scheduled with (host.hpp: RoundLadder;
+// empty: uniform caps).  Step k holds the largest entry cap of which k images fit kSweepLdsLimit,
+// for kSweepCus * k resident blocks, down to the sweep's own cap.  An image is sized for the
+// sweep's row limit -- a chain's launch mixes rounds of both shapes -- and holds one direction at a
+// time (the fused last round stages its backward entries over the forward ones)
+RoundLadder round_ladder(const EngineOpts &o, bool dist);
 // every option as "name=value;name=value;..." (the effective sweep, and sweep_set as its own
 // entry), and the inverse: a spec of that form applied on top of o
 std::string engine_opts_string(const EngineOpts &o, bool dist);
@@ -393,8 +408,14 @@ struct DFactor {
     bool no_chain = false;  // engine option no_chain (set before make_dfactor)
     int chain_wide = 256;   // engine option chain_wide
     std::vector<int64_t> round_ptr;  // host copy: blocks per round
-    std::vector<char> round_fits;    // host: every block of round r fits (sweep_rows[1], sweep_cap[1])
+    std::vector<char> round_fits;    // host: every block of round r fits the round's rows and cap (rows_of, cap_of)
     int sweep_rows[2] = {192, 1024}, sweep_cap[2] = {576, 4096}, sweep_threads[2] = {64, 512};  // round 0 / rest
+    // the schedule's per-round caps (Schedule::round_cap / round_rows; empty: the uniform ones above)
+    std::vector<int32_t> round_cap, round_rows;
+    int cap_of(int64_t r) const { return (size_t)r < round_cap.size() ? round_cap[(size_t)r] : sweep_cap[r == 0 ? 0 : 1]; }
+    int rows_of(int64_t r) const { return (size_t)r < round_rows.size() ? round_rows[(size_t)r] : sweep_rows[r == 0 ? 0 : 1]; }
+    // a round whose blocks may hold more entries than the block kernels stage in one pass
+    bool tall(int64_t r) const { return r > 0 && cap_of(r) > sweep_cap[1]; }
     size_t bytes() const {
         return fptr.bytes() + fcol.bytes() + fcol16.bytes() + ufold.bytes() + ustep.bytes() + ucode[0].bytes() + ucode[1].bytes() + urlead.bytes() + urblk[0].bytes() + urblk[1].bytes() + urrow[0].bytes() + urrow[1].bytes() + urtab[0].bytes() + urtab[1].bytes() + fval.bytes() + bptr.bytes() + bcol.bytes() + bval.bytes() + D.bytes() +
                perm.bytes() + blk_lvl.bytes() + lvl_row.bytes() + meta.bytes();

@@ -359,8 +359,10 @@ static void height_levels(const Factor &f, LdlSymbolic *sym) {
 }
 
 Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, int64_t CAP1, int64_t SUB0,
-                        const std::vector<int64_t> *extra_bwd, const std::vector<int64_t> *extra_fwd) {
+                        const std::vector<int64_t> *extra_bwd, const std::vector<int64_t> *extra_fwd,
+                        const RoundLadder *ladder) {
     if (SUB0 <= 0 || SUB0 > CAP0) SUB0 = CAP0;
+    if (ladder && (ladder->steps.empty() || ladder->rows < 1)) ladder = nullptr;
     const int64_t N = f.N;
     SubClock clk;
     Schedule s;
@@ -379,9 +381,18 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
     });
     const int64_t u0 = std::max<int64_t>(1, CAP0 / std::max<int64_t>(R0, 1));
     const int64_t u1 = std::max<int64_t>(1, CAP1 / std::max<int64_t>(R1, 1));
-    auto wt0 = [&](int64_t v) { return std::max<int64_t>(u0, ent[v]); };
     auto wt1 = [&](int64_t v) { return std::max<int64_t>(u1, ent[v]); };
-    auto capof = [&](int32_t r) { return r == 0 ? CAP0 : CAP1; };
+    // per round: the entry cap, the least weight of a row (cap / row limit) and the row limit.  A
+    // round the ladder gave a larger cap is listed in tall; every other round has the uniform caps
+    struct RoundCap {
+        int64_t cap, u, rows;
+    };
+    std::vector<RoundCap> tall;  // by round; cap == 0: uniform
+    auto capof = [&](int32_t r) {
+        if (r == 0) return RoundCap{CAP0, u0, R0};
+        if ((size_t)r < tall.size() && tall[(size_t)r].cap) return tall[(size_t)r];
+        return RoundCap{CAP1, u1, R1};
+    };
     // children lists and the tree height (for reporting), one ascending pass each
     std::vector<int32_t> cptr(N + 2, 0), height(N, 0);
     for (int64_t v = 0; v < N; v++) {
@@ -409,22 +420,49 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
     std::unique_ptr<int64_t[]> sz(new int64_t[N]);
     std::unique_ptr<int32_t[]> root_of(new int32_t[N]);
     int32_t round = 0;
-    while (!alive.empty()) {
+    // one round's peel of the alive rows with least row weight u and subtree cap CAP: sz and
+    // root_of (a root has root_of[v] == v); returns the blocks its clusters pack into at pack_cap
+    auto peel = [&](int64_t u, int64_t CAP, int64_t pack_cap) {
         for (int32_t v : alive) sz[v] = 0;
-        const int64_t u = round == 0 ? u0 : u1;
-        // round 0 peels subtrees of weight <= SUB0 and packs several of them per block
-        const int64_t CAP = round == 0 ? SUB0 : capof(round);
         for (int32_t v : alive) {  // ascending: children before parents
             sz[v] += std::max<int64_t>(u, ent[v]);
             if (f.parent[v] >= 0 && is_alive[f.parent[v]]) sz[f.parent[v]] += sz[v];
         }
-        const size_t before = alive.size();
         for (size_t q = alive.size(); q-- > 0;) {  // descending: parents before children
             const int32_t v = alive[q], p = f.parent[v];
             if (sz[v] > CAP) root_of[v] = -1;
-            else if (p < 0 || sz[p] > CAP) root_of[v] = v, closed_round[v] = round;
+            else if (p < 0 || sz[p] > CAP) root_of[v] = v;
             else root_of[v] = root_of[p];
         }
+        int64_t blocks = 0, fill = pack_cap + 1;  // the packing below, counted
+        for (int32_t v : alive)
+            if (root_of[v] == v) {
+                if (fill + sz[v] > pack_cap) blocks++, fill = 0;
+                fill += sz[v];
+            }
+        return blocks;
+    };
+    while (!alive.empty()) {
+        // round 0 peels subtrees of weight <= SUB0 and packs several of them per block
+        bool peeled = false;
+        if (ladder && round >= 2)  // the largest cap whose blocks are all resident at once
+            for (const auto &st : ladder->steps) {
+                if (st.first <= CAP1) break;
+                const int64_t u = (st.first + ladder->rows - 1) / ladder->rows;
+                if (peel(u, st.first, st.first) > st.second) continue;
+                tall.resize((size_t)round + 1, RoundCap{0, 0, 0});
+                tall[(size_t)round] = RoundCap{st.first, u, ladder->rows};
+                peeled = true;
+                break;
+            }
+        if (!peeled) {
+            const int64_t nb = peel(round == 0 ? u0 : u1, round == 0 ? SUB0 : CAP1, round == 0 ? CAP0 : CAP1);
+            // a round 1 that the device holds at once: a narrow top, its schedule stays as it is
+            if (ladder && round == 1 && nb <= ladder->min_round1) ladder = nullptr;
+        }
+        const size_t before = alive.size();
+        for (int32_t v : alive)
+            if (root_of[v] == v) closed_round[v] = round;
         std::vector<int32_t> rest;
         rest.reserve(alive.size());
         for (int32_t v : alive) {
@@ -436,6 +474,9 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
         if (!alive.empty() && round >= 8 && alive.size() * 2 > before) break;  // chain-like tree
     }
     clk.lap("schedule: layer peeling");
+    // a chain-like tree (the peeling gave up): the clustering below closes clusters of (R1, CAP1)
+    // into whatever round they fall, so such a schedule keeps uniform caps
+    if (!alive.empty() && !tall.empty()) return build_schedule(f, R0, CAP0, R1, CAP1, SUB0, extra_bwd, extra_fwd, nullptr);
     // (2) Greedy bottom-up clustering of what peeling left (chain-like upper trees): a node's
     //     open cluster absorbs its children's open clusters, closing the largest ones until it
     //     fits in R rows.  Peeled children are already-closed clusters.
@@ -479,7 +520,7 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
         const bool root = closed_round[v] >= 0;
         const int32_t c = root ? (int32_t)v : cl[f.parent[v]];
         cl[v] = c;
-        const int64_t w = closed_round[c] == 0 ? wt0(v) : wt1(v);
+        const int64_t w = std::max<int64_t>(capof(closed_round[c]).u, ent[v]);
         csize[c] = root ? w : csize[c] + w;
     }
     clk.lap("schedule: clustering");
@@ -491,7 +532,7 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
     int32_t nb = 0;
     s.round_ptr.assign(1, 0);
     for (int32_t r = 0; r < nrounds; r++) {
-        const int64_t cap = capof(r);
+        const int64_t cap = capof(r).cap;
         int64_t fill = cap + 1;
         for (int32_t c : roots_by_round[r]) {
             if (fill + csize[c] > cap) {
@@ -503,6 +544,9 @@ Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, i
         }
         s.round_ptr.push_back(nb);
     }
+    if (!tall.empty())
+        for (int32_t r = 0; r < nrounds; r++)
+            s.round_cap.push_back((int32_t)capof(r).cap), s.round_rows.push_back((int32_t)capof(r).rows);
     // new order: blocks ascending (= rounds ascending), then level, then old index
     std::vector<int32_t> block(N);
     std::vector<int64_t> bcount(nb + 1, 0);

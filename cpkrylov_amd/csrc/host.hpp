@@ -175,6 +175,23 @@ struct Schedule {
     std::vector<int64_t> lvl_row;      // level boundaries (row positions), one array for all blocks
     int64_t max_levels = 0;
     int64_t depth = 0;
+    // per round: the entry cap and row limit its blocks were built for (build_schedule's ladder;
+    // empty: round 0 has (R0, CAP0) and every upper round (R1, CAP1))
+    std::vector<int32_t> round_cap, round_rows;
+};
+// Per-round block caps of the upper rounds (engine option round_caps).  Round 1 keeps (R1, CAP1);
+// a later round peels with the first step of the ladder -- (entry cap, blocks the device keeps
+// resident at that cap), caps descending -- whose block count stays within the step's limit, and
+// with (R1, CAP1) where none does.  A step's blocks hold at most `rows` rows (the row-span
+// loop's limit).  The ladder applies to a tree whose round 1 has more than min_round1 blocks --
+// more than the device keeps resident, the sign of a deep upper tree (the +-64 window's 8207
+// blocks and 15 rounds against the +-4 window's 1024 and 4); a narrower tree keeps uniform
+// caps.  The ladder is fixed at analysis time from gfx950's constants (round_ladder,
+// opts.cpp), so every rank and host builds the same schedule.
+struct RoundLadder {
+    std::vector<std::pair<int64_t, int64_t>> steps;
+    int64_t rows = 128;
+    int64_t min_round1 = 0;
 };
 // Round 0 (the wide bottom of the tree) uses blocks of (R0 rows, CAP0 entries); the upper
 // rounds use (R1, CAP1), typically larger so that few launches cover the top of the tree.
@@ -183,8 +200,12 @@ struct Schedule {
 // per block cuts the barrier-separated level passes per row.
 // extra_bwd[v] / extra_fwd[v]: backward / forward entries of row v outside the factor (the
 // distributed separators' backward terms into T; T's own forward terms on the exchanged payload)
+// ladder (optional): per-round caps for the rounds above round 1 (RoundLadder); null or empty:
+// uniform caps, today's schedule.  A chain-like tree that the peeling does not finish keeps
+// uniform caps too.
 Schedule build_schedule(const Factor &f, int64_t R0, int64_t CAP0, int64_t R1, int64_t CAP1, int64_t SUB0 = 0,
-                        const std::vector<int64_t> *extra_bwd = nullptr, const std::vector<int64_t> *extra_fwd = nullptr);
+                        const std::vector<int64_t> *extra_bwd = nullptr, const std::vector<int64_t> *extra_fwd = nullptr,
+                        const RoundLadder *ladder = nullptr);
 // Apply the schedule's relabel to the factor (values unchanged, exact data movement).
 // src (optional): src[t] = index into f.Li / f.Lx of the relabelled factor's entry t.
 Factor relabel(const Factor &f, const Schedule &s, std::vector<int32_t> *src = nullptr);

@@ -390,6 +390,7 @@ struct RsOut {
     std::vector<int16_t> *code = nullptr;  // [2]: DFactor::ucode's host copies (the destinations go there)
     const uint32_t *code0 = nullptr;       // [2]
     size_t cap_bytes = 0;
+    std::vector<size_t> round_bytes;       // per round where the schedule has per-round caps (else cap_bytes)
     std::vector<int16_t> lead;
     std::vector<RsBlk> blk[2];
     std::vector<RsRow> row[2];
@@ -451,6 +452,10 @@ void rowspan_export(const Factor &f, const Schedule &s, int64_t block, int dir, 
     out.step.assign((size_t)nr, 0);
     for (int t = 0; t < nr; t++) out.step[(size_t)order[(size_t)t].second] = dir ? nr - 1 - t : t;
     RsLayout L;
+    if (!s.round_cap.empty()) {  // per-round caps: the block's own round's
+        const size_t rnd = (size_t)(std::upper_bound(s.round_ptr.begin(), s.round_ptr.end(), block) - s.round_ptr.begin()) - 1;
+        sched_cap = s.round_cap[std::min(rnd, s.round_cap.size() - 1)];
+    }
     const size_t cap = rowspan_cap_bytes((int)(cap_entries > 0 ? cap_entries : sched_cap));
     out.eligible = rowspan_layout((int)r0, (int)r1, ptr, out.col, [&](int k) { return (int)out.step[(size_t)k]; }, cap, L);
     if (!out.eligible) return;
@@ -484,6 +489,7 @@ void mark_dataflow(std::vector<int32_t> &meta, const std::vector<int64_t> &round
     std::vector<size_t> round_cap(round_ptr.size() - 1, rs_on ? rs->cap_bytes : 0);
     if (rs_on)
         for (size_t r = 1; r + 1 < round_ptr.size(); r++) {
+            if (r < rs->round_bytes.size()) round_cap[r] = rs->round_bytes[r];
             if (round_ptr[r + 1] - round_ptr[r] <= kRowspanNarrowRound) continue;
             int cap = 1;
             for (int64_t b = round_ptr[r]; b < round_ptr[r + 1]; b++)
@@ -752,14 +758,17 @@ void make_dfactor(const Factor &f, const Schedule &s, DFactor &d, const std::vec
     if (fsrc) *fsrc = std::move(fidx);
     if (bsrc) *bsrc = std::move(bidx);
     // rounds whose blocks all fit the upper-round staging image (sptrsv_upper_kernel)
+    d.round_cap = s.round_cap, d.round_rows = s.round_rows;
     d.round_fits.assign(s.round_ptr.empty() ? 0 : s.round_ptr.size() - 1, 1);
-    for (size_t r = 0; r < d.round_fits.size(); r++)
+    for (size_t r = 0; r < d.round_fits.size(); r++) {
+        // (round 0 against the upper rounds' shape, as before the per-round caps: it is not read for it)
+        const int64_t rows = d.tall((int64_t)r) ? d.rows_of((int64_t)r) : d.sweep_rows[1];
+        const uint32_t cap = (uint32_t)(d.tall((int64_t)r) ? d.cap_of((int64_t)r) : d.sweep_cap[1]);
         for (int64_t b = s.round_ptr[r]; b < s.round_ptr[r + 1]; b++) {
             const int64_t r0 = s.lvl_row[s.blk_lvl[b]], r1 = s.lvl_row[s.blk_lvl[b + 1]];
-            if (r1 - r0 > d.sweep_rows[1] || fptr[r1] - fptr[r0] > (uint32_t)d.sweep_cap[1] ||
-                bptr[r1] - bptr[r0] > (uint32_t)d.sweep_cap[1])
-                d.round_fits[r] = 0;
+            if (r1 - r0 > rows || fptr[r1] - fptr[r0] > cap || bptr[r1] - bptr[r0] > cap) d.round_fits[r] = 0;
         }
+    }
     // padding entries: clamped, unconditional loads may touch one entry past a block's end
     fcol.resize(fcol.size() + kFactorPadEntries, 0), bcol.resize(bcol.size() + kFactorPadEntries, 0);
     clk.lap("layout: round fits, padding");
@@ -806,6 +815,7 @@ void make_dfactor(const Factor &f, const Schedule &s, DFactor &d, const std::vec
         const std::vector<int16_t> us = build_ufold(d, meta, s.round_ptr, fptr, fcol, bptr, bcol, [&](int64_t q) { return K(q); }, code);
         RsOut rs;
         rs.code = code, rs.code0 = d.ucode0, rs.cap_bytes = rowspan_cap_bytes(d.sweep_cap[1]);
+        for (size_t r = 0; r + 1 < s.round_ptr.size(); r++) rs.round_bytes.push_back(rowspan_cap_bytes(d.cap_of((int64_t)r)));
         mark_dataflow(meta, s.round_ptr, fptr, fcol, bptr, bcol, d.dataflow, d.colsweep, us, d.urow0, &d.hmodel, d.rowspan, &rs);
         upload_rowspan(d, code, rs, s.round_ptr.size() >= 3 ? s.round_ptr[1] : 0);
     }
@@ -1795,6 +1805,15 @@ static Img launch_img(const DFactor &F, int64_t b0, int64_t b1, int rmax, int ca
     return Img{std::min(it->second.first, rmax), std::min(it->second.second, capmax)};
 }
 static size_t img_bytes(const Img &g) { return sweep_lds_bytes(g.R, g.CAP); }
+// the dynamic LDS a block kernel is admitted: its own image, or the limit where a schedule with
+// per-round caps may launch it with a tall round's image (DFactor::tall)
+static size_t kernel_lds_max(size_t own) { return std::max(own, kSweepLdsLimit); }
+// the image of a launch that holds tall blocks [b0, b1): their largest rows and entries
+static Img tall_img(const DFactor &F, int64_t b0, int64_t b1) {
+    const Img g = launch_img(F, b0, b1, INT32_MAX, INT32_MAX);
+    if (img_bytes(g) > kSweepLdsLimit) throw Error(CPK_ERR_UNSUPPORTED, "internal: a tall round's image exceeds the LDS limit");
+    return g;
+}
 static inline UFold ufold_of(const DFactor &F) {
     const bool cs = F.ustep.n && F.ucode[0].n && F.ucode[1].n;
     UFold u{F.ufold.n ? F.ufold.p : nullptr, cs ? F.ustep.p : nullptr, F.urow0, cs ? F.ucode[0].p : nullptr,
@@ -2607,7 +2626,9 @@ __device__ __forceinline__ void wst(double *p, double v) {
 struct NoWait {
     __device__ void operator()() const {}
 };
-template <int TPB, int RPU, int EPU, bool BWD, bool ADD, bool SC = false, class Wait = NoWait>
+// TALL: the block may hold more than EPU * TPB entries (a round with a cap of its own); the kernels
+// of a uniform schedule are compiled without the chunk loop
+template <int TPB, int RPU, int EPU, bool BWD, bool ADD, bool SC = false, class Wait = NoWait, bool TALL = false>
 __device__ __forceinline__ void upper_block(
     char *smem, const BlkMeta m, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
@@ -2729,6 +2750,32 @@ __device__ __forceinline__ void upper_block(
             }
         }
     }
+    // a tall block (a round with a cap of its own, build_schedule's ladder): the entries behind the
+    // first EPU * TPB, a chunk at a time through the same registers into the one image -- entries,
+    // staged columns, gathers and stores exactly as above (the codes go out with the entries: loaded
+    // at the stores they are a third dependent round trip per chunk, 152 -> 207 us per chain launch)
+    if constexpr (TALL) {
+        for (int e00 = EPU * TPB; e00 < ne; e00 += EPU * TPB) {
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                const uint32_t ec = e0 + (uint32_t)(e < ne ? e : 0);
+                c[u] = __builtin_nontemporal_load(col + ec), v[u] = __builtin_nontemporal_load(val + ec);
+                cl[u] = cs ? (int32_t)(uint16_t)(BWD ? uf.cb[ec - uf.cb0] : uf.cf[ec - uf.cf0]) : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < EPU; u++) g[u] = wld<SC>(w + ((c[u] >= r0 && c[u] < r1) ? r0 : c[u]));
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                if (e < ne) {
+                    const bool local = c[u] >= r0 && c[u] < r1;
+                    if (!rs) S.c[e] = (int16_t)(cs ? cl[u] : (local ? c[u] - r0 : R));
+                    S.v[rs ? cl[u] : e] = local ? v[u] : v[u] * g[u];
+                }
+            }
+        }
+    }
     __syncthreads();
     CPK_UP_STAMP(0);
     if (uf.p) fold_known<TPB>(S, nr, tid);
@@ -2777,7 +2824,7 @@ __device__ __forceinline__ void upper_block(
     CPK_UP_STAMP(3);
 }
 
-template <int TPB, int RPU, int EPU, bool BWD, bool ADD>
+template <int TPB, int RPU, int EPU, bool BWD, bool ADD, bool TALL = false>
 __global__ __launch_bounds__(TPB) void sptrsv_upper_kernel(
     int64_t blk0, const BlkMeta *__restrict__ meta, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
@@ -2786,8 +2833,9 @@ __global__ __launch_bounds__(TPB) void sptrsv_upper_kernel(
     UFold uf, Img img) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip(run, active)) return;
-    upper_block<TPB, RPU, EPU, BWD, ADD>(smem, meta[blk0 + blockIdx.x], lvl_row, ptr, col, val, D, perm, xin, neg_from,
-                                         w, out, sched_in, ys, xs, pk, uf, blk0 + blockIdx.x, img);
+    upper_block<TPB, RPU, EPU, BWD, ADD, false, NoWait, TALL>(smem, meta[blk0 + blockIdx.x], lvl_row, ptr, col, val, D, perm,
+                                                              xin, neg_from, w, out, sched_in, ys, xs, pk, uf,
+                                                              blk0 + blockIdx.x, img);
 }
 
 // The last round's forward and backward sweeps in one launch (single GPU).  The sweeps meet at
@@ -2798,7 +2846,7 @@ __global__ __launch_bounds__(TPB) void sptrsv_upper_kernel(
 // forward fold and levels, divides by D in LDS and runs the backward levels -- the operations of
 // sptrsv_upper_kernel forward, its write-back and w / D, and sptrsv_upper_kernel backward, in
 // that order: bit-identical, one launch and one staging round trip fewer per solve.
-template <int TPB, int RPU, int EPU, bool ADD, bool SC = false, class Wait = NoWait>
+template <int TPB, int RPU, int EPU, bool ADD, bool SC = false, class Wait = NoWait, bool TALL = false>
 __device__ __forceinline__ void last_block(
     char *smem, const BlkMeta m, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ fptr, const int32_t *__restrict__ fcol, const double *__restrict__ fval,
@@ -2906,6 +2954,29 @@ __device__ __forceinline__ void last_block(
             S.v[rsf ? cl[u] : e] = local ? vf[u] : vf[u] * g[u];
         }
     }
+    // a tall block's forward entries behind the first EPU * TPB (upper_block's chunk loop)
+    if constexpr (TALL) {
+        for (int e00 = EPU * TPB; e00 < nef; e00 += EPU * TPB) {
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                const uint32_t ef = (uint32_t)m.fe0 + (uint32_t)(e < nef ? e : 0);
+                cf[u] = __builtin_nontemporal_load(fcol + ef), vf[u] = __builtin_nontemporal_load(fval + ef);
+                cl[u] = csf ? (int32_t)(uint16_t)uf.cf[ef - uf.cf0] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < EPU; u++) g[u] = wld<SC>(w + ((cf[u] >= r0 && cf[u] < r1) ? r0 : cf[u]));
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                if (e < nef) {
+                    const bool local = cf[u] >= r0 && cf[u] < r1;
+                    if (!rsf) S.c[e] = (int16_t)(csf ? cl[u] : (local ? cf[u] - r0 : R));
+                    S.v[rsf ? cl[u] : e] = local ? vf[u] : vf[u] * g[u];
+                }
+            }
+        }
+    }
     RsRow rw[2];
     if (rsf && tid < kWave) rowspan_rows(uf.rr[0] + (r0 - uf.row0), nr, tid, rw);
     __syncthreads();
@@ -2954,6 +3025,30 @@ __device__ __forceinline__ void last_block(
             S.v[rsb ? (int)cd : e] = local ? vb[u] : vb[u] * g[u];
         }
     }
+    // ... and its backward entries behind the first EPU * TPB
+    if constexpr (TALL) {
+        for (int e00 = EPU * TPB; e00 < neb; e00 += EPU * TPB) {
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                const uint32_t eb = (uint32_t)m.be0 + (uint32_t)(e < neb ? e : 0);
+                cb[u] = __builtin_nontemporal_load(bcol + eb), vb[u] = __builtin_nontemporal_load(bval + eb);
+                cl[u] = csb ? (int32_t)(uint16_t)uf.cb[eb - uf.cb0] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < EPU; u++)
+                g[u] = (e00 + tid + u * TPB < neb && (cb[u] < r0 || cb[u] >= r1)) ? wld<SC>(w + cb[u]) : 0.0;
+#pragma unroll
+            for (int u = 0; u < EPU; u++) {
+                const int e = e00 + tid + u * TPB;
+                if (e < neb) {
+                    const bool local = cb[u] >= r0 && cb[u] < r1;
+                    if (!rsb) S.c[e] = (int16_t)(csb ? cl[u] : (local ? cb[u] - r0 : R));
+                    S.v[rsb ? cl[u] : e] = local ? vb[u] : vb[u] * g[u];
+                }
+            }
+        }
+    }
     if (rsb && tid < kWave) rowspan_rows(uf.rr[1] + (r0 - uf.row0), nr, tid, rw);
     __syncthreads();
     if (uf.p) fold_known<TPB>(S, nr, tid);
@@ -2978,7 +3073,7 @@ __device__ __forceinline__ void last_block(
     }
 }
 
-template <int TPB, int RPU, int EPU, bool ADD>
+template <int TPB, int RPU, int EPU, bool ADD, bool TALL = false>
 __global__ __launch_bounds__(TPB) void sptrsv_last_kernel(
     int64_t blk0, const BlkMeta *__restrict__ meta, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ fptr, const int32_t *__restrict__ fcol, const double *__restrict__ fval,
@@ -2988,8 +3083,9 @@ __global__ __launch_bounds__(TPB) void sptrsv_last_kernel(
     Img img) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (skip(run, active)) return;
-    last_block<TPB, RPU, EPU, ADD>(smem, meta[blk0 + blockIdx.x], lvl_row, fptr, fcol, fval, bptr, bcol, bval, D, perm,
-                                   xin, neg_from, sched_in, xs, w, out, ys, uf, blk0 + blockIdx.x, img);
+    last_block<TPB, RPU, EPU, ADD, false, NoWait, TALL>(smem, meta[blk0 + blockIdx.x], lvl_row, fptr, fcol, fval, bptr, bcol,
+                                                        bval, D, perm, xin, neg_from, sched_in, xs, w, out, ys, uf,
+                                                        blk0 + blockIdx.x, img);
 }
 
 // the last round fused (fwd + bwd) when it is an upper round whose blocks fit sptrsv_last_kernel
@@ -3000,30 +3096,37 @@ bool fuse_last_ok(const DFactor &F) {
            (int64_t)F.round_fits.size() >= R && F.round_fits[R - 1] && !F.no_upper;
 }
 
-static void launch_last(Ctx &c, const DFactor &F, const FwdIn &in, double *w, double *out, bool add,
-                        const int *run, const int *active, double *ys) {
+template <bool TALL>
+static void launch_last_t(Ctx &c, const DFactor &F, const FwdIn &in, double *w, double *out, bool add,
+                          const int *run, const int *active, double *ys) {
     constexpr int TPB = 512, RPU = 2, EPU = 8;
     const int64_t R = (int64_t)F.round_ptr.size() - 1;
     const int64_t b0 = F.round_ptr[R - 1], nb = F.round_ptr[R] - b0;
     if (!nb) return;
-    const size_t lds = sweep_lds_bytes(RPU * TPB, EPU * TPB);
-    const Img img{RPU * TPB, EPU * TPB};
+    const size_t own = sweep_lds_bytes(RPU * TPB, EPU * TPB), lds = TALL ? kernel_lds_max(own) : own;
+    // (a tall last round: its own rows and entries, staged in chunks of EPU * TPB)
+    const Img img = TALL ? tall_img(F, b0, b0 + nb) : Img{RPU * TPB, EPU * TPB};
     static const bool lds_ok = lds <= 64 * 1024 ||
-        (hipFuncSetAttribute((const void *)sptrsv_last_kernel<TPB, RPU, EPU, false>,
+        (hipFuncSetAttribute((const void *)sptrsv_last_kernel<TPB, RPU, EPU, false, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-         hipFuncSetAttribute((const void *)sptrsv_last_kernel<TPB, RPU, EPU, true>,
+         hipFuncSetAttribute((const void *)sptrsv_last_kernel<TPB, RPU, EPU, true, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
     if (!lds_ok) throw Error(CPK_ERR_HIP, "sptrsv_last_kernel: LDS image not admitted");
     const BlkMeta *meta = reinterpret_cast<const BlkMeta *>(F.meta.p);
     if (add)
-        hipLaunchKernelGGL((sptrsv_last_kernel<TPB, RPU, EPU, true>), dim3((unsigned)nb), dim3(TPB), img_bytes(img), c.stream, b0,
+        hipLaunchKernelGGL((sptrsv_last_kernel<TPB, RPU, EPU, true, TALL>), dim3((unsigned)nb), dim3(TPB), img_bytes(img), c.stream, b0,
                            meta, F.lvl_row.p, F.fptr.p, F.fcol.p, F.fval.p, F.bptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p,
                            in.xin, in.neg_from, in.sched_in, in.xs, w, out, run, active, ys, ufold_of(F), img);
     else
-        hipLaunchKernelGGL((sptrsv_last_kernel<TPB, RPU, EPU, false>), dim3((unsigned)nb), dim3(TPB), img_bytes(img), c.stream, b0,
+        hipLaunchKernelGGL((sptrsv_last_kernel<TPB, RPU, EPU, false, TALL>), dim3((unsigned)nb), dim3(TPB), img_bytes(img), c.stream, b0,
                            meta, F.lvl_row.p, F.fptr.p, F.fcol.p, F.fval.p, F.bptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p,
                            in.xin, in.neg_from, in.sched_in, in.xs, w, out, run, active, ys, ufold_of(F), img);
     CPK_HIP(hipGetLastError());
+}
+static void launch_last(Ctx &c, const DFactor &F, const FwdIn &in, double *w, double *out, bool add,
+                        const int *run, const int *active, double *ys) {
+    if (F.tall((int64_t)F.round_ptr.size() - 2)) launch_last_t<true>(c, F, in, w, out, add, run, active, ys);
+    else launch_last_t<false>(c, F, in, w, out, add, run, active, ys);
 }
 
 // ---- the sweep chains ----------------------------------------------------------------------------
@@ -3090,7 +3193,7 @@ __device__ __forceinline__ void st_agent32(uint32_t *p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int TPB, int RPU, int EPU, bool ADD>
+template <int TPB, int RPU, int EPU, bool ADD, bool TALL = false>
 __global__ __launch_bounds__(TPB) void sptrsv_chain_kernel(
     ChainArgs ch, const BlkMeta *__restrict__ meta, const int32_t *__restrict__ lvl_row,
     const uint32_t *__restrict__ fptr, const int32_t *__restrict__ fcol, const double *__restrict__ fval,
@@ -3144,14 +3247,15 @@ __global__ __launch_bounds__(TPB) void sptrsv_chain_kernel(
 #endif
     };
     if (kind == 0)
-        upper_block<TPB, RPU, EPU, false, false, true>(smem, meta[b], lvl_row, fptr, fcol, fval, D, perm, xin, neg_from, w,
-                                                       nullptr, sched_in, nullptr, xs, pk, uf, b, img, wait);
+        upper_block<TPB, RPU, EPU, false, false, true, decltype(wait), TALL>(smem, meta[b], lvl_row, fptr, fcol, fval, D, perm, xin,
+                                                                             neg_from, w, nullptr, sched_in, nullptr, xs, pk, uf,
+                                                                             b, img, wait);
     else if (kind == 1)
-        last_block<TPB, RPU, EPU, ADD, true>(smem, meta[b], lvl_row, fptr, fcol, fval, bptr, bcol, bval, D, perm, xin,
-                                             neg_from, sched_in, xs, w, out, ys, uf, b, img, wait);
+        last_block<TPB, RPU, EPU, ADD, true, decltype(wait), TALL>(smem, meta[b], lvl_row, fptr, fcol, fval, bptr, bcol, bval, D,
+                                                                   perm, xin, neg_from, sched_in, xs, w, out, ys, uf, b, img, wait);
     else
-        upper_block<TPB, RPU, EPU, true, ADD, true>(smem, meta[b], lvl_row, bptr, bcol, bval, D, perm, nullptr, 0, w, out,
-                                                    0, ys, nullptr, pk, uf, b, img, wait);
+        upper_block<TPB, RPU, EPU, true, ADD, true, decltype(wait), TALL>(smem, meta[b], lvl_row, bptr, bcol, bval, D, perm, nullptr,
+                                                                          0, w, out, 0, ys, nullptr, pk, uf, b, img, wait);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's w stores done
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -3299,35 +3403,46 @@ static bool chain_ok(const DFactor &F, int kind) {
     return F.chain[kind].ntask > 0 && !F.no_chain && (kind != kChainFull || fuse_last_ok(F));
 }
 
-template <int TPB, int RPU, int EPU>
+template <int TPB, int RPU, int EPU, bool TALL>
 static void launch_chain_t(Ctx &c, const DFactor &F, int kind, const FwdIn &in, double *w, double *out, bool add,
                            const int *run, const int *active, double *ys, const PackArgs &pk) {
     const DChain &h = F.chain[kind];
-    const size_t lds = std::max<size_t>(sweep_lds_bytes(RPU * TPB, EPU * TPB), (size_t)CPK_CHAIN_LDS_MIN);
+    const size_t own = std::max<size_t>(sweep_lds_bytes(RPU * TPB, EPU * TPB), (size_t)CPK_CHAIN_LDS_MIN);
+    const size_t lds = TALL ? kernel_lds_max(own) : own;
     static const bool lds_ok = lds <= 64 * 1024 ||
-        (hipFuncSetAttribute((const void *)sptrsv_chain_kernel<TPB, RPU, EPU, false>,
+        (hipFuncSetAttribute((const void *)sptrsv_chain_kernel<TPB, RPU, EPU, false, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-         hipFuncSetAttribute((const void *)sptrsv_chain_kernel<TPB, RPU, EPU, true>,
+         hipFuncSetAttribute((const void *)sptrsv_chain_kernel<TPB, RPU, EPU, true, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
     if (!lds_ok) throw Error(CPK_ERR_HIP, "sptrsv_chain_kernel: LDS image not admitted");
-    const Img img{RPU * TPB, EPU * TPB};  // narrow rounds: every task resident at the kernel's image
+    // narrow rounds: every task resident at the kernel's image; with a tall round among them, at
+    // the image of the chain's largest block (one workgroup per CU either way: the floor below)
+    const Img img = TALL ? tall_img(F, F.round_ptr[F.chain_first], F.round_ptr.back()) : Img{RPU * TPB, EPU * TPB};
     const BlkMeta *meta = reinterpret_cast<const BlkMeta *>(F.meta.p);
     const size_t ldsb = std::max<size_t>(img_bytes(img), (size_t)CPK_CHAIN_LDS_MIN);
     const ChainArgs ch{h.task.p, h.dptr.p, h.didx.p, h.flag.p, h.ctrl.p, (int)h.ntask};
     if (add)
-        hipLaunchKernelGGL((sptrsv_chain_kernel<TPB, RPU, EPU, true>), dim3((unsigned)h.ntask), dim3(TPB), ldsb, c.stream,
+        hipLaunchKernelGGL((sptrsv_chain_kernel<TPB, RPU, EPU, true, TALL>), dim3((unsigned)h.ntask), dim3(TPB), ldsb, c.stream,
                            ch, meta, F.lvl_row.p, F.fptr.p, F.fcol.p, F.fval.p, F.bptr.p, F.bcol.p, F.bval.p, F.D.p,
                            F.perm.p, in.xin, in.neg_from, in.sched_in, in.xs, w, out, run, active, ys, pk, ufold_of(F), img);
     else
-        hipLaunchKernelGGL((sptrsv_chain_kernel<TPB, RPU, EPU, false>), dim3((unsigned)h.ntask), dim3(TPB), ldsb,
+        hipLaunchKernelGGL((sptrsv_chain_kernel<TPB, RPU, EPU, false, TALL>), dim3((unsigned)h.ntask), dim3(TPB), ldsb,
                            c.stream, ch, meta, F.lvl_row.p, F.fptr.p, F.fcol.p, F.fval.p, F.bptr.p, F.bcol.p, F.bval.p,
                            F.D.p, F.perm.p, in.xin, in.neg_from, in.sched_in, in.xs, w, out, run, active, ys, pk, ufold_of(F), img);
     CPK_HIP(hipGetLastError());
 }
 static void launch_chain(Ctx &c, const DFactor &F, int kind, const FwdIn &in, double *w, double *out, bool add,
                          const int *run, const int *active, double *ys, const PackArgs &pk) {
-    if (F.chain[kind].tpb == 512) launch_chain_t<512, 2, 8>(c, F, kind, in, w, out, add, run, active, ys, pk);
-    else launch_chain_t<256, 2, 12>(c, F, kind, in, w, out, add, run, active, ys, pk);
+    bool tall = false;  // a chained round with a cap of its own: the kernels with the chunk loop
+    for (int64_t r = F.chain_first; r + 1 < (int64_t)F.round_ptr.size(); r++) tall = tall || F.tall(r);
+    if (F.chain[kind].tpb == 512) {
+        if (tall) launch_chain_t<512, 2, 8, true>(c, F, kind, in, w, out, add, run, active, ys, pk);
+        else launch_chain_t<512, 2, 8, false>(c, F, kind, in, w, out, add, run, active, ys, pk);
+    } else if (tall) {
+        launch_chain_t<256, 2, 12, true>(c, F, kind, in, w, out, add, run, active, ys, pk);
+    } else {
+        launch_chain_t<256, 2, 12, false>(c, F, kind, in, w, out, add, run, active, ys, pk);
+    }
 }
 
 void check_chain(const DFactor &F) {
@@ -3342,22 +3457,23 @@ void check_chain(const DFactor &F) {
     }
 }
 
-template <int TPB, int RPU, int EPU>
+template <int TPB, int RPU, int EPU, bool TALL>
 static bool upper_round_t(Ctx &c, const DFactor &F, int64_t r, bool bwd, bool add, const double *xin,
                           int64_t neg_from, double *w, double *out, const int *run, const int *active, int sched_in,
                           double *ys, double *xs, const PackArgs &pk) {
     if (F.sweep_threads[1] != TPB || F.sweep_rows[1] > RPU * TPB || F.sweep_cap[1] > EPU * TPB ||
-        r >= (int64_t)F.round_fits.size() || !F.round_fits[r])
+        r >= (int64_t)F.round_fits.size() || !F.round_fits[r] || F.tall(r) != TALL)
         return false;
     const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
     if (!nb) return true;
-    const size_t lds = sweep_lds_bytes(RPU * TPB, EPU * TPB);  // the kernel's image (>= the configured block)
+    // the kernel's image (>= the configured block), or a tall round's
+    const size_t own = sweep_lds_bytes(RPU * TPB, EPU * TPB), lds = TALL ? kernel_lds_max(own) : own;
     static const bool lds_ok = lds <= 64 * 1024 ||
-        (hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, false, false>,
+        (hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, false, false, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-         hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, true, true>,
+         hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, true, true, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-         hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, true, false>,
+         hipFuncSetAttribute((const void *)sptrsv_upper_kernel<TPB, RPU, EPU, true, false, TALL>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
     if (!lds_ok) return false;
     const BlkMeta *meta = reinterpret_cast<const BlkMeta *>(F.meta.p);
@@ -3371,18 +3487,20 @@ static bool upper_round_t(Ctx &c, const DFactor &F, int64_t r, bool bwd, bool ad
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         return (int64_t)cus * (int64_t)std::max<size_t>(1, (160 * 1024) / sweep_lds_bytes(RPU * TPB, EPU * TPB));
     }();
-    const Img img = nb > resident ? launch_img(F, b0, b0 + nb, RPU * TPB, EPU * TPB) : Img{RPU * TPB, EPU * TPB};
+    // (a tall round: the image of its largest block, which the ladder keeps resident)
+    const Img img = TALL ? tall_img(F, b0, b0 + nb)
+                         : nb > resident ? launch_img(F, b0, b0 + nb, RPU * TPB, EPU * TPB) : Img{RPU * TPB, EPU * TPB};
     const size_t ldsr = img_bytes(img);
     if (!bwd)
-        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, false, false>), dim3((unsigned)nb), dim3(TPB), ldsr,
+        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, false, false, TALL>), dim3((unsigned)nb), dim3(TPB), ldsr,
                            c.stream, b0, meta, F.lvl_row.p, F.fptr.p, F.fcol.p, F.fval.p, F.D.p, F.perm.p, xin,
                            neg_from, w, out, run, active, sched_in, ys, xs, pk, ufold_of(F), img);
     else if (add)
-        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, true, true>), dim3((unsigned)nb), dim3(TPB), ldsr,
+        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, true, true, TALL>), dim3((unsigned)nb), dim3(TPB), ldsr,
                            c.stream, b0, meta, F.lvl_row.p, F.bptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p, xin,
                            neg_from, w, out, run, active, sched_in, ys, xs, pk, ufold_of(F), img);
     else
-        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, true, false>), dim3((unsigned)nb), dim3(TPB), ldsr,
+        hipLaunchKernelGGL((sptrsv_upper_kernel<TPB, RPU, EPU, true, false, TALL>), dim3((unsigned)nb), dim3(TPB), ldsr,
                            c.stream, b0, meta, F.lvl_row.p, F.bptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p, xin,
                            neg_from, w, out, run, active, sched_in, ys, xs, pk, ufold_of(F), img);
     return true;
@@ -3397,8 +3515,10 @@ static bool upper_round(Ctx &c, const DFactor &F, int64_t r, bool bwd, bool add,
     if (F.no_upper) return false;
     // 256 threads (blocks of <= 512 rows / 3072 entries, a 38 KB image): four blocks per CU, for a
     // schedule whose first upper round has more blocks than 512-thread images keep resident
-    return upper_round_t<512, 2, 8>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk) ||
-           upper_round_t<256, 2, 12>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk);
+    return upper_round_t<512, 2, 8, false>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk) ||
+           upper_round_t<256, 2, 12, false>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk) ||
+           upper_round_t<512, 2, 8, true>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk) ||
+           upper_round_t<256, 2, 12, true>(c, F, r, bwd, add, xin, neg_from, w, out, run, active, sched_in, ys, xs, pk);
 }
 
 // SPLIT > 1: the workgroup is one wave holding SPLIT independent logical blocks of TPB lanes

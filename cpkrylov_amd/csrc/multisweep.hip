@@ -239,11 +239,10 @@ const MultiPlan &multisweep_plan(const DFactor &F) {
     p.staged = p.direct = 0;
     if (F.hmeta.size() < (size_t)F.nblk * 8) throw Error(CPK_ERR_UNSUPPORTED, "internal: factor without block records");
     for (int64_t r = 0; r < nr; r++) {
-        const int i = r == 0 ? 0 : 1;
         for (int64_t b = F.round_ptr[r]; b < F.round_ptr[r + 1]; b++) {
             const int32_t *m = &F.hmeta[(size_t)b * 8];
             const int rows = m[1] - m[0], nef = m[5] - m[4], neb = m[7] - m[6];
-            if (!multi_staged(rows, nef, neb, F.sweep_rows[i], F.sweep_cap[i], limit)) {
+            if (!multi_staged(rows, nef, neb, F.rows_of(r), F.cap_of(r), limit)) {
                 p.direct++;
                 continue;
             }
@@ -266,11 +265,10 @@ void multi_fwd_rounds(Ctx &c, const DFactor &F, const double *Xp, int64_t ldx, i
     const int64_t R = (int64_t)F.round_ptr.size() - 1;
     const int limit = multi_lds_limit();
     for (int64_t r = 0; r < R; r++) {
-        const int i = r == 0 ? 0 : 1;
         const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
         if (!nb) continue;
         hipLaunchKernelGGL((multisweep_kernel<false, MODE>), dim3((unsigned)nb), dim3(kMultiThreads), p.lds[(size_t)r * 2],
-                           c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p, F.lvl_row.p, F.fptr.p,
+                           c.stream, b0, F.rows_of(r), F.cap_of(r), limit, F.blk_lvl.p, F.lvl_row.p, F.fptr.p,
                            F.bptr.p, F.fcol.p, F.fval.p, F.D.p, F.perm.p, Xp, ldx, (double *)nullptr, (int64_t)0, kc, panel,
                            1, ref);
     }
@@ -282,12 +280,11 @@ void multi_bwd_rounds(Ctx &c, const DFactor &F, double *Yp, int64_t ldy, int kc,
     const int64_t R = (int64_t)F.round_ptr.size() - 1;
     const int limit = multi_lds_limit();
     for (int64_t r = R - 1; r >= 0; r--) {
-        const int i = r == 0 ? 0 : 1;
         const int64_t b0 = F.round_ptr[r], nb = F.round_ptr[r + 1] - b0;
         if (!nb) continue;
         // the backward sweep's last round: nothing reads its staged blocks' panel rows again
         hipLaunchKernelGGL((multisweep_kernel<true, MODE>), dim3((unsigned)nb), dim3(kMultiThreads),
-                           p.lds[(size_t)r * 2 + 1], c.stream, b0, F.sweep_rows[i], F.sweep_cap[i], limit, F.blk_lvl.p,
+                           p.lds[(size_t)r * 2 + 1], c.stream, b0, F.rows_of(r), F.cap_of(r), limit, F.blk_lvl.p,
                            F.lvl_row.p, F.bptr.p, F.fptr.p, F.bcol.p, F.bval.p, F.D.p, F.perm.p, (const double *)nullptr,
                            (int64_t)0, Yp, ldy, kc, panel, r == 0 ? 0 : 1, ref);
     }

@@ -1,5 +1,6 @@
 // opts.cpp -- engine options of a context (dev.hpp: EngineOpts).  A context copies the
 // CPK_<NAME> environment variables once at creation; cpk_ctx_set_option changes its copy.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -94,6 +95,31 @@ SweepConfig dist_sweep_default() {
 
 SweepConfig effective_sweep(const EngineOpts &o, bool dist) { return (dist && !o.sweep_set) ? dist_sweep_default() : o.sweep; }
 
+RoundLadder round_ladder(const EngineOpts &o, bool dist) {
+    RoundLadder L;
+    if (!o.round_caps || o.sweep_set || dist) return L;
+    const SweepConfig &sw = o.sweep;
+    const int rows = std::max(sw.rows[1], (int)L.rows);
+    auto largest = [&](int k) {  // the largest cap of which k images fit
+        int64_t cap = (int64_t)(kSweepLdsLimit / (size_t)k / 10);
+        while (cap > 0 && (size_t)k * sweep_lds_bytes(rows, (int)cap) > kSweepLdsLimit) cap--;
+        return cap;
+    };
+    if (o.round_caps > 1) {  // forced: every round above round 1 at this cap, whatever its block count
+        const int64_t cap = std::min<int64_t>(o.round_caps, largest(1));
+        if (cap > sw.cap[1]) L.steps.push_back({cap, INT64_MAX});
+        return L;
+    }
+    // (a round 1 within the blocks resident at the sweep's own image leaves the schedule alone)
+    L.min_round1 = kSweepCus * (int64_t)(kSweepLdsLimit / sweep_lds_bytes(sw.rows[1], sw.cap[1]));
+    for (int k = 1;; k++) {
+        const int64_t cap = largest(k);
+        if (cap <= sw.cap[1]) break;
+        L.steps.push_back({cap, kSweepCus * k});
+    }
+    return L;
+}
+
 void set_engine_option(EngineOpts &o, const std::string &name, const std::string &value) {
     for (const BoolOpt &b : kBool)
         if (name == b.name) {
@@ -132,6 +158,12 @@ void set_engine_option(EngineOpts &o, const std::string &name, const std::string
         if (!ok)
             throw Error(CPK_ERR_ARGS, "engine option fail_inject: expected R:setup, R:batch:K or R:chain:K, got '" + value + "'");
         o.fail_inject = value;
+    } else if (name == "round_caps") {
+        char *end = nullptr;
+        const long v = strtol(value.c_str(), &end, 10);
+        if (end == value.c_str() || *end != '\0' || v < 0 || v > 16384)
+            throw Error(CPK_ERR_ARGS, "engine option round_caps must be an integer in [0, 16384], got '" + value + "'");
+        o.round_caps = (int)v;
     } else if (name == "chain_wide") {
         char *end = nullptr;
         const long v = strtol(value.c_str(), &end, 10);
@@ -161,6 +193,7 @@ std::string get_engine_option(const EngineOpts &o, const std::string &name, bool
     if (name == "batch") return std::to_string(o.batch);
     if (name == "r0_xcd_chunk") return std::to_string(o.r0_xcd_chunk);
     if (name == "chain_wide") return std::to_string(o.chain_wide);
+    if (name == "round_caps") return std::to_string(o.round_caps);
     if (name == "fail_inject") return o.fail_inject;
     throw Error(CPK_ERR_ARGS, "unknown engine option '" + name + "'");
 }
@@ -179,6 +212,7 @@ EngineOpts engine_opts_from_env() {
     from("batch");
     from("r0_xcd_chunk");
     from("chain_wide");
+    from("round_caps");
     from("fail_inject");
     return o;
 }
@@ -194,6 +228,7 @@ std::string engine_opts_string(const EngineOpts &o, bool dist) {
     put("batch");
     put("r0_xcd_chunk");
     put("chain_wide");
+    put("round_caps");
     put("fail_inject");
     return s;
 }
@@ -230,6 +265,7 @@ uint64_t engine_opts_hash(const EngineOpts &o) {
     mix(std::to_string(o.batch));
     mix(std::to_string(o.r0_xcd_chunk));
     mix(std::to_string(o.chain_wide));
+    mix(std::to_string(o.round_caps));
     // fail_inject is rank-local by design (a test hook): not hashed, so the plan agreement passes
     return h;
 }

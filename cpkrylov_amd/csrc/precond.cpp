@@ -65,8 +65,9 @@ Analysis analyze(const HCsr &A11, const HCsr &B, const HCsr &C22, const EngineOp
     try {
         an.sweep = o.sweep;
         if (global_schedule) {
+            const RoundLadder ladder = round_ladder(o, false);  // the single-GPU default sweep's per-round caps
             an.S = build_schedule(f0, an.sweep.rows[0], an.sweep.cap[0], an.sweep.rows[1], an.sweep.cap[1],
-                                  an.sweep.sub0, nullptr);
+                                  an.sweep.sub0, nullptr, nullptr, &ladder);
             pc.lap("schedule");
             an.F = relabel(f0, an.S, device_numeric ? &an.rsrc : nullptr);
             pc.lap("relabel");

@@ -146,7 +146,9 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * (the upper rounds' row-span level loop: never / on every eligible block instead of where the host
  * model picks it; all_rowspan goes before all_dataflow and all_colsweep, which otherwise keep
  * their loop on every block they force), no_chain, chain_wide
- * (rounds of at most this many blocks join the sweep chain, default 256), exact_dots, no_bcast_analysis
+ * (rounds of at most this many blocks join the sweep chain, default 256), round_caps (per-round block
+ * caps above round 1, single GPU with the default sweep: 0 uniform caps, 1 (default) the largest cap
+ * whose blocks stay resident, N > 1 every such round at N entries), exact_dots, no_bcast_analysis
  * (every rank of a distributed preconditioner runs the global analysis instead of receiving rank 0's),
  * apply_multi_panel (cpk_pc_apply_multi always on its panel kernels; set before building operators),
  * no_sched_resid, no_fused_resid, r0_xcd_chunk, tsolve_global, tsolve_sweep,
@@ -382,6 +384,10 @@ int cpk_analysis_pivot_shift(cpk_analysis an, double *E);
  * descending row -- the order of the reference's column-oriented solves. */
 int cpk_analysis_schedule(cpk_analysis an, int64_t *nlevels, int64_t *round_ptr, int64_t *blk_lvl,
                           int64_t *lvl_row, int32_t *order);
+/* The caps each round's blocks were built for (engine option round_caps): cap[nrounds] entries of
+ * either direction, rows[nrounds] rows per block.  A schedule with uniform caps reports the sweep
+ * option's: round 0's pair, then the upper rounds' for every other round. */
+int cpk_analysis_round_caps(cpk_analysis an, int32_t *cap, int32_t *rows);
 
 /* ---- distributed plan (host-only) --------------------------------- */
 /* The row-block plan of rank `rank` out of `nranks` for the system the analysis was built on
