@@ -160,6 +160,22 @@ _SIGS = {
                          P(C.c_double)], C.c_int),
     "cpk_kkt_adjoint_device": ([vp, vp, C.c_int, vp, vp, vp, P(Opts), vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp,
                                 C.c_int64, P(Stats), P(C.c_double)], C.c_int),
+    "cpk_kkt_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, P(Opts), P(C.c_double), C.c_int64,
+                             C.c_int, P(Stats), P(C.c_int), P(C.c_double)], C.c_int),
+    "cpk_kkt_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, P(Opts), vp, C.c_int64, C.c_int, P(Stats),
+                                    P(C.c_int), P(C.c_double)], C.c_int),
+    "cpk_kkt_sample_multi": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64,
+                              P(C.c_double), C.c_int64, P(C.c_double), C.c_int64], C.c_int),
+    "cpk_kkt_sample_multi_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
+                                     C.c_int64], C.c_int),
+    "cpk_kkt_set_sample_route": ([vp, C.c_int], C.c_int),
+    "cpk_kkt_sample_route_info": ([vp, P(C.c_int64)], C.c_int),
+    "cpk_kkt_adjoint_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, vp, P(Opts),
+                               P(C.c_double), C.c_int64, C.c_int, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64,
+                               P(C.c_double), C.c_int64, P(Stats), P(C.c_int), P(C.c_double)], C.c_int),
+    "cpk_kkt_adjoint_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, P(Opts), vp, C.c_int64,
+                                      C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, P(Stats), P(C.c_int),
+                                      P(C.c_double)], C.c_int),
     "cpk_method_solve_multi": ([vp, C.c_int, C.c_int64, P(C.c_double), C.c_int64, vp, vp, vp, P(Opts), P(C.c_double),
                                 C.c_int64, P(C.c_double), C.c_int64, P(Stats), P(C.c_int)], C.c_int),
     "cpk_method_solve_multi_device": ([vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, P(Opts), vp, C.c_int64,

@@ -1355,6 +1355,199 @@ class KKT:
         stats["true_resid"] = _norms_dict(res[4:], True)
         return dict(db=lam, dA=out.get("dA"), dB=out.get("dB"), dC=out.get("dC"), stats=stats, flag=flag)
 
+    # ---- the block forms: N x k blocks (a (k, N) row-major device tensor is the N x k block) ----------
+    def _host_cols(self, a, what):
+        """An N x k Fortran-ordered float64 copy of a host block (a vector is one column)"""
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2 or a.shape[0] != self.N:
+            raise CpkError(_lib.CPK_ERR_DIM, f"{what} must have N = {self.N} rows")
+        return np.array(a, dtype=np.float64, order="F")
+
+    def _device_cols(self, vs, whats):
+        """The addresses of device blocks of one shape, their column count and leading dimension"""
+        ptrs, k = [], None
+        for v, what in zip(vs, whats):
+            if not _is_device(v):
+                raise CpkError(_lib.CPK_ERR_ARGS, f"{what}: the operands are all host arrays or all device tensors")
+        for v, what in zip(vs, whats):
+            p, kv, ld = _device_operand(v, what, self.N)
+            if k is not None and kv != k:
+                raise CpkError(_lib.CPK_ERR_DIM, f"{what} must have the other operands' shape")
+            k = kv
+            ptrs.append(p)
+        return ptrs, k, max(self.N, 1)
+
+    def _block_method(self, method, M, *operands):
+        name = getattr(method, "_cpk_method", method)
+        if name not in _lib.METHODS:
+            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+        if any(isinstance(v, Operator) for v in (M,) + operands):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K's block entries are matrix-only: K's (1,1) block is the matrix it was built on")
+        if not isinstance(M, opLDL2):
+            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        return name
+
+    def _block_stats(self, sts, stats, res, k):
+        for j in range(k):
+            stats[j]["ptime"], stats[j]["stime"] = sts[j].ptime, sts[j].stime
+            stats[j]["true_resid0"] = _norms_dict(res[8 * j:8 * j + 4], True)
+            stats[j]["true_resid"] = _norms_dict(res[8 * j + 4:8 * j + 8], True)
+
+    def solve_block(self, method, B, M, opts=None, X0=None, out=None):
+        """X, stats, flags = K.solve_block(method, B, M, opts, X0): `solve` for the k columns of an
+        N x k block in lockstep (cpk_kkt_solve_multi; cpcg and cpminres, the other methods raise
+        CPK_ERR_UNSUPPORTED).  Column j is K.solve(method, B[:, j], M, opts, x0=X0[:, j]): with X0
+        (one start for the whole block) every column's stop test runs on its correction system.
+        stats and flags are lists of k dicts, each stats with `true_resid0` and `true_resid`.
+        Device operands as `residual` takes blocks: B a (k, N) device tensor, the result in out=,
+        and a warm start passes X0=out.  A column whose driver stops raises its error carrying
+        `columns` (the per-column status codes) and `partial` = (X, stats, flags)."""
+        name = self._block_method(method, M, B, X0, out)
+        if _is_device(B):
+            if out is None or not _is_device(out):
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_block on device operands: pass the result tensor as out=")
+            if X0 is not None and X0 is not out:
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_block on device operands: X0 is out itself (updated in place)")
+            (bp, xp), k, ld = self._device_cols((B, out), ("B", "out"))
+            X, entry, args = out, lib.cpk_kkt_solve_multi_device, (bp, xp)
+        else:
+            if _is_device(X0) or _is_device(out):
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_block: B, X0 and out are all host arrays or all device tensors")
+            Bf = self._host_cols(B, "B")
+            k, ld = Bf.shape[1], max(self.N, 1)
+            X = np.zeros((self.N, k), order="F") if out is None else out
+            if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.shape == (self.N, k) and
+                    (X.flags.f_contiguous or k == 0)):
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_block: out is a Fortran-ordered float64 N x k array")
+            if X0 is not None:
+                X0f = self._host_cols(X0, "X0")
+                if X0f.shape != Bf.shape:
+                    raise CpkError(_lib.CPK_ERR_DIM, "X0 must have B's shape")
+                X[...] = X0f
+            entry, args = lib.cpk_kkt_solve_multi, (_dptr(Bf), _dptr(X))
+        res = np.zeros(8 * max(k, 1))
+
+        def call(sts, status):
+            return entry(self.h, _lib.METHODS[name], k, args[0], ld, M.h, C.byref(make_opts(opts)), args[1], ld,
+                         int(X0 is not None), sts, status, _dptr(res))
+
+        sts, stats, flags, err = _block_call(name, k, opts, self.n, self.m, call, True)
+        self._block_stats(sts, stats, res, k)
+        if err is not None:
+            err.partial = (X, stats, flags)
+            raise err
+        return X, stats, flags
+
+    def _grad_args(self, out, device):
+        """The six gradient arguments of the C entries from out= (host: all three, created where
+        absent; device: those present)"""
+        counts = [h.info()["entries"] for h in (self.A, self.B, self.C)]
+        gp = []
+        for key, cnt in zip(("dA", "dB", "dC"), counts):
+            g = out.get(key)
+            if device:
+                if g is None:
+                    gp += [C.c_void_p(None), 0]
+                    continue
+                if not _is_device(g):
+                    raise CpkError(_lib.CPK_ERR_ARGS, f"out[{key!r}] is a device tensor, as the operands are")
+                gp += [_device_operand(g, key, cnt)[0], int(g.numel())]
+            else:
+                if g is None:
+                    g = out[key] = np.zeros(cnt)
+                if not (isinstance(g, np.ndarray) and g.dtype == np.float64 and g.flags.c_contiguous):
+                    raise CpkError(_lib.CPK_ERR_ARGS, f"out[{key!r}] is a contiguous float64 array")
+                gp += [_dptr(g) if g.size else None, g.size]
+        return gp
+
+    def set_sample_route(self, route):
+        """Routing of `sample_block`'s kernel: "auto" (by the measured rule: the panel kernel where the
+        last panel of 8 columns is full), "panel" (the panel
+        kernel on interleaved copies of X and Lam, k >= 2) or "outer" (the run-time-k kernel of
+        `Matrix.sample_outer` on the blocks themselves); the same bits on either."""
+        check(lib.cpk_kkt_set_sample_route(self.h, {"auto": 0, "panel": 1, "outer": 2}[route]))
+
+    def sample_route_info(self):
+        v = (C.c_int64 * 4)()
+        check(lib.cpk_kkt_sample_route_info(self.h, v))
+        return {"panel_columns": v[0], "max_pad": v[1], "route": ("auto", "panel", "outer")[v[2]], "panel_calls": v[3]}
+
+    def sample_block(self, X, Lam, out=None):
+        """dict(dA, dB, dC) = K.sample_block(X, Lam): the three gradient passes alone
+        (cpk_kkt_sample_multi), the sums over the k columns of -lam_x x_x', -(lam_y x_x' + x_y lam_x')
+        and +lam_y x_y' sampled on the sparsity of K's A, B and C, each in the order its handle's
+        `set_values` takes.  Per entry the products are added in column order from 0.0, each rounded
+        on its own.  Host blocks: out= may hold NumPy arrays to fill.  Device tensors: out= is a
+        dict of device tensors; a gradient that is absent is not formed."""
+        out = dict(out or {})
+        if set(out) - {"dA", "dB", "dC"}:
+            raise CpkError(_lib.CPK_ERR_ARGS, "sample_block: out= holds dA, dB, dC")
+        if _is_device(X) or _is_device(Lam):
+            (xp, lp), k, ld = self._device_cols((X, Lam), ("X", "Lam"))
+            check(lib.cpk_kkt_sample_multi_device(self.h, k, xp, ld, lp, ld, *self._grad_args(out, True)))
+        else:
+            Xf, Lf = self._host_cols(X, "X"), self._host_cols(Lam, "Lam")
+            if Xf.shape != Lf.shape:
+                raise CpkError(_lib.CPK_ERR_DIM, "Lam must have X's shape")
+            gp = self._grad_args(out, False)
+            check(lib.cpk_kkt_sample_multi(self.h, Xf.shape[1], _dptr(Xf), max(self.N, 1), _dptr(Lf), max(self.N, 1), *gp))
+        return dict(dA=out.get("dA"), dB=out.get("dB"), dC=out.get("dC"))
+
+    def adjoint_block(self, method, X, GX, M, opts=None, Lam0=None, out=None):
+        """The adjoint of `solve_block` (cpk_kkt_adjoint_multi): with X = K \\ B and GX = dL/dX
+        returns dict(db, dA, dB, dC, stats, flags), db = Lam = K \\ GX by
+        `solve_block(method, GX, M, opts, X0=Lam0)` (stats and flags are that call's lists) and dA,
+        dB, dC = `sample_block(X, Lam)`: the gradients of the batch, summed over its columns.  There
+        is no KT: the caller asserts that A is symmetric.  Host and device operands as `adjoint`
+        takes them: on device, out["db"] is required and Lam0 is out["db"] itself.  A column whose
+        driver stops raises its error (`columns`, `partial` = (Lam, stats, flags)); the gradient
+        arrays are then untouched."""
+        name = self._block_method(method, M, X, GX, Lam0)
+        out = dict(out or {})
+        if set(out) - {"db", "dA", "dB", "dC"}:
+            raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block: out= holds db, dA, dB, dC")
+        device = _is_device(X) or _is_device(GX)
+        if device:
+            if not _is_device(out.get("db")):
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block on device operands: X, GX and out['db'] are device tensors")
+            if Lam0 is not None and Lam0 is not out["db"]:
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block on device operands: Lam0 is out['db'] itself (updated in place)")
+            (xp, gxp, lp), k, ld = self._device_cols((X, GX, out["db"]), ("X", "GX", "out['db']"))
+            entry = lib.cpk_kkt_adjoint_multi_device
+        else:
+            if _is_device(Lam0) or any(_is_device(v) for v in out.values()):
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block: the operands are all host arrays or all device tensors")
+            Xf, Gf = self._host_cols(X, "X"), self._host_cols(GX, "GX")
+            if Xf.shape != Gf.shape:
+                raise CpkError(_lib.CPK_ERR_DIM, "GX must have X's shape")
+            k, ld = Xf.shape[1], max(self.N, 1)
+            lam = out.setdefault("db", np.zeros((self.N, k), order="F"))
+            if not (isinstance(lam, np.ndarray) and lam.dtype == np.float64 and lam.shape == (self.N, k) and
+                    (lam.flags.f_contiguous or k == 0)):
+                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block: out['db'] is a Fortran-ordered float64 N x k array")
+            if Lam0 is not None:
+                L0 = self._host_cols(Lam0, "Lam0")
+                if L0.shape != Xf.shape:
+                    raise CpkError(_lib.CPK_ERR_DIM, "Lam0 must have X's shape")
+                lam[...] = L0
+            xp, gxp, lp = _dptr(Xf), _dptr(Gf), _dptr(lam)
+            entry = lib.cpk_kkt_adjoint_multi
+        gp = self._grad_args(out, device)
+        res = np.zeros(8 * max(k, 1))
+
+        def call(sts, status):
+            return entry(self.h, _lib.METHODS[name], k, xp, ld, gxp, ld, M.h, C.byref(make_opts(opts)), lp, ld,
+                         int(Lam0 is not None), *gp, sts, status, _dptr(res))
+
+        sts, stats, flags, err = _block_call(name, k, opts, self.n, self.m, call, True)
+        self._block_stats(sts, stats, res, k)
+        if err is not None:
+            err.partial = (out["db"], stats, flags)
+            raise err
+        return dict(db=out["db"], dA=out.get("dA"), dB=out.get("dB"), dC=out.get("dC"), stats=stats, flags=flags)
+
     def __del__(self):
         if getattr(self, "h", None):
             lib.cpk_kkt_destroy(self.h)

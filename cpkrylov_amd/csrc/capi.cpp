@@ -198,6 +198,15 @@ struct cpk_kkt_s {
     int64_t panels = 0;
     DBuf<double> Tp;
     DBuf<double> ws;  // cpk_kkt_solve's vectors (kkt_solve_core), allocated by the first solve and kept
+    // the block forms (cpk_kkt_solve_multi, cpk_kkt_sample_multi), each grown on first use and kept:
+    // the warm start's residual and correction blocks (2 N k), the device side of the sums (12 k) and
+    // the sampler's operands: the interleaved panels of X and Lam (2 * panel_count(k) * 8 N) or, on the
+    // other route, gB's staged 2 k columns (2 k N)
+    DBuf<double> wsb, normsb, panel_ops;
+    // the block sampler's routing (0: by sample_panel_rule, 1: always the panel kernel, 2: always the
+    // run-time-k kernel) and the calls that took the panel kernel so far
+    int sample_route = 0;
+    int64_t sample_panels = 0;
     // the operator on the handles' current values: a device gather where a values generation
     // moved (the value array keeps its address; nothing goes through the host)
     const DMat &current() {
@@ -1524,6 +1533,275 @@ int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *Bh, in
                                           so.bt_colmin, p, opts, dX.d.p, dX.ld(), stats, col_status, &msg);
     dX.down(X, ldx);
     return solve_multi_result(rc, msg);
+    API_END
+}
+
+// ---- the block forms of the verified solve and of its adjoint --------------------------------------
+// Column j is cpk_kkt_solve on B(:, j): the driver is reg_solve_multi_device unchanged (no routing by
+// k), the start sums are launch_kkt_sums of b_j (cold) or the block residual's (warm), the last four
+// those of one block residual of the returned X.  The checks first, so a refusal writes nothing.
+static void check_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double *B, int64_t ldb, cpk_pc M, const double *X,
+                                  int64_t ldx) {
+    need(K && M && ((B && X) || !(K->n + K->m)), "NULL argument");
+    const int64_t N = K->n + K->m;
+    if (k < 0 || ldb < N || ldx < N)
+        throw Error(CPK_ERR_DIM, "kkt_solve_multi: k >= 0 and leading dimensions >= N required");
+    need(M->ctx == K->ctx, "kkt_solve_multi: M belongs to another context");
+    check_method_dims(K->A, K->C, M);
+    require_block_solve(K->ctx->c, *M->p, method);
+}
+
+// res: host, 8 k (or null).  Returns CPK_OK or the first failing column's status (message in *msg)
+static int kkt_solve_multi_core(cpk_kkt K, int method, int64_t k, const double *d_B, int64_t ldb, cpk_pc M,
+                                const cpk_opts *opts, double *d_X, int64_t ldx, int warm, cpk_stats *stats, int *col_status,
+                                double *res, std::string *msg) {
+    if (k == 0) return CPK_OK;
+    cpk_mat A = K->A, C = K->C;
+    Ctx &c = K->ctx->c;
+    Precond &p = *M->p;
+    const int64_t N = K->n + K->m, N1 = std::max<int64_t>(N, 1);
+    const DMat &Kd = K->current();
+    const DMat &AC = A->krylov_op(C, p);
+    const ShiftOps so = shift_ops(A, C, p);
+    // [8 k: the call's sums, column by column; 4 k: a block residual's sums before they are spread]
+    if (K->normsb.n < 12 * (size_t)k) K->normsb.alloc(12 * (size_t)k);
+    double *dn = K->normsb.p, *dt = dn + 8 * k;
+    auto spread = [&](int at) {  // dt[4 j ..] -> dn[8 j + at ..]
+        CPK_HIP(hipMemcpy2DAsync(dn + at, 8 * sizeof(double), dt, 4 * sizeof(double), 4 * sizeof(double), (size_t)k,
+                                 hipMemcpyDeviceToDevice, c.stream));
+    };
+    int rc;
+    if (!warm) {
+        for (int64_t j = 0; j < k; j++) {
+            if (N) CPK_HIP(hipMemsetAsync(d_X + j * ldx, 0, N * sizeof(double), c.stream));
+            launch_kkt_sums(c, Kd, K->n, d_B + j * ldb, d_B + j * ldb, dn + 8 * j);
+        }
+        rc = reg_solve_multi_device(c, method, k, d_B, ldb, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_X, ldx, stats,
+                                    col_status, msg);
+    } else {
+        const size_t blk = (size_t)N1 * (size_t)k;
+        if (K->wsb.n < 2 * blk) K->wsb.alloc(2 * blk);
+        double *R = K->wsb.p, *dX = R + blk;
+        CPK_HIP(hipMemsetAsync(dX, 0, blk * sizeof(double), c.stream));
+        kkt_resid_block(K, k, d_X, ldx, d_B, ldb, R, N1, dt);
+        spread(0);
+        rc = reg_solve_multi_device(c, method, k, R, N1, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dX, N1, stats, col_status,
+                                    msg);
+        for (int64_t j = 0; j < k; j++) launch_recover(c, N, d_X + j * ldx, dX + j * N1, d_X + j * ldx);
+    }
+    kkt_resid_block(K, k, d_X, ldx, d_B, ldb, nullptr, 0, dt);
+    spread(4);
+    if (res) CPK_HIP(hipMemcpyAsync(res, dn, 8 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    return rc;
+}
+
+int cpk_kkt_solve_multi_device(cpk_kkt K, int method, int64_t k, const double *d_B, int64_t ldb, cpk_pc M,
+                               const cpk_opts *opts, double *d_X, int64_t ldx, int warm, cpk_stats *stats, int *col_status,
+                               double *res) {
+    API_BEGIN
+    check_kkt_solve_multi(K, method, k, d_B, ldb, M, d_X, ldx);
+    std::string msg;
+    const int rc = kkt_solve_multi_core(K, method, k, d_B, ldb, M, opts, d_X, ldx, warm, stats, col_status, res, &msg);
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+int cpk_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double *B, int64_t ldb, cpk_pc M, const cpk_opts *opts,
+                        double *X, int64_t ldx, int warm, cpk_stats *stats, int *col_status, double *res) {
+    API_BEGIN
+    check_kkt_solve_multi(K, method, k, B, ldb, M, X, ldx);
+    if (k == 0) return CPK_OK;
+    const int64_t N = K->n + K->m;
+    HostBlock dB(N, k), dX(N, k);
+    dB.up(B, ldb);
+    if (warm) dX.up(X, ldx);
+    std::string msg;
+    const int rc = kkt_solve_multi_core(K, method, k, dB.d.p, dB.ld(), M, opts, dX.d.p, dX.ld(), warm, stats, col_status, res,
+                                        &msg);
+    dX.down(X, ldx);
+    return solve_multi_result(rc, msg);
+    API_END
+}
+
+// The three gradient passes of a block: X and Lam (N x k) onto the sparsity of K's handles.  From
+// kSamplePanelMinCols columns the interleaved panels and the panel kernel (adjoint.hip); k = 1 is the
+// single-column adjoint's three launches, k = 0 writes alpha * 0.0
+static void check_kkt_sample(cpk_kkt K, int64_t k, const double *X, int64_t ldx, const double *L, int64_t ldl,
+                             const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC, int64_t cC) {
+    need(K && ((X && L) || !(K->n + K->m) || k == 0), "NULL argument");
+    const int64_t N = K->n + K->m;
+    if (k < 0 || k > INT32_MAX / 2 || ldx < N || ldl < N)
+        throw Error(CPK_ERR_DIM, "kkt_sample_multi: k >= 0 and leading dimensions >= N required");
+    const cpk_mat_s *h[3] = {K->A, K->B, K->C};
+    const double *g[3] = {gA, gB, gC};
+    const int64_t cnt[3] = {cA, cB, cC};
+    for (int i = 0; i < 3; i++)
+        if (g[i] && cnt[i] != h[i]->vm.count)
+            throw Error(CPK_ERR_DIM, "kkt_sample_multi: a gradient's count differs from its handle's creating call's entry count");
+    if (K->ctx->c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "kkt_sample_multi: single-GPU only");
+}
+
+static void kkt_sample_core(cpk_kkt K, int64_t k, const double *d_X, int64_t ldx, const double *d_L, int64_t ldl,
+                            double *d_gA, double *d_gB, double *d_gC) {
+    if (!d_gA && !d_gB && !d_gC) return;
+    Ctx &c = K->ctx->c;
+    const int64_t n = K->n, N = K->n + K->m;
+    auto dev = [&](cpk_mat_s *H) -> const DMat & {
+        const DMat &d = H->dev();
+        upload_value_map(H->vm, H->dvm);
+        return d;
+    };
+    // k < 2 has no panel path; from there the measured rule (or the forced route) decides, and either
+    // path gives every entry the same bits
+    const bool panel = k >= 2 && (K->sample_route == 1 || (K->sample_route == 0 && sample_panel_rule(k)));
+    if (!panel) {
+        auto pass = [&](cpk_mat_s *H, int64_t kk, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
+                        double *out) {
+            if (out) launch_sample_outer(c, dev(H), H->vm, H->dvm, kk, U, ldu, V, ldv, alpha, out);
+        };
+        pass(K->A, k, d_L, ldl, d_X, ldx, -1.0, d_gA);
+        pass(K->C, k, d_L + n, ldl, d_X + n, ldx, 1.0, d_gC);
+        if (!d_gB) return;
+        if (k <= 1) {
+            // gB's 2 k columns alternate between the two blocks (kkt_adjoint_core): for one column that
+            // is a column stride from Lam to X and back
+            const int64_t l2x = ((int64_t)(intptr_t)d_X - (int64_t)(intptr_t)d_L) / (int64_t)sizeof(double);
+            pass(K->B, 2 * k, d_L + n, l2x, d_X, -l2x, -1.0, d_gB);
+            return;
+        }
+        // for more columns one stride cannot express the alternation: the 2 k columns
+        // U = [ly_0, xy_0, ly_1, ...] (m rows) and V = [xx_0, lx_0, xx_1, ...] (n rows) are staged by
+        // four strided copies
+        const int64_t m = K->m, m1 = std::max<int64_t>(m, 1), n1 = std::max<int64_t>(n, 1);
+        const size_t need_d = 2 * (size_t)k * (size_t)(m1 + n1);
+        if (K->panel_ops.n < need_d) K->panel_ops.alloc(need_d);
+        double *U = K->panel_ops.p, *V = U + 2 * (size_t)k * (size_t)m1;
+        auto stage = [&](double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows) {
+            if (rows)
+                CPK_HIP(hipMemcpy2DAsync(dst, 2 * (size_t)ldd * sizeof(double), src, (size_t)lds * sizeof(double),
+                                         (size_t)rows * sizeof(double), (size_t)k, hipMemcpyDeviceToDevice, c.stream));
+        };
+        stage(U, m1, d_L + n, ldl, m), stage(U + m1, m1, d_X + n, ldx, m);
+        stage(V, n1, d_X, ldx, n), stage(V + n1, n1, d_L, ldl, n);
+        pass(K->B, 2 * k, U, m1, V, n1, -1.0, d_gB);
+        return;
+    }
+    K->sample_panels++;
+    const int64_t ps = N * kMultiKP;  // one panel of an array
+    const size_t per = (size_t)panel_count(k) * (size_t)ps;
+    if (K->panel_ops.n < 2 * per) K->panel_ops.alloc(2 * per);
+    double *PX = K->panel_ops.p, *PL = PX + per;
+    launch_pack_panels(c, N, k, d_X, ldx, d_L, ldl, PX, PL);
+    const double *xx = PX, *xy = PX + n * kMultiKP, *lx = PL, *ly = PL + n * kMultiKP;
+    auto pass = [&](cpk_mat_s *H, const double *U1, const double *V1, const double *U2, const double *V2, double alpha,
+                    double *out) {
+        if (out) launch_sample_panel(c, dev(H), H->vm, H->dvm, k, ps, U1, V1, U2, V2, alpha, out);
+    };
+    pass(K->A, lx, xx, nullptr, nullptr, -1.0, d_gA);  // -sum_c lx_c * xx_c'
+    pass(K->B, ly, xx, xy, lx, -1.0, d_gB);            // -sum_c (ly_c * xx_c' then xy_c * lx_c')
+    pass(K->C, ly, xy, nullptr, nullptr, 1.0, d_gC);   // +sum_c ly_c * xy_c' (K holds -C)
+}
+
+int cpk_kkt_set_sample_route(cpk_kkt K, int route) {
+    API_BEGIN
+    need(K != nullptr, "NULL argument");
+    need(route >= 0 && route <= 2, "kkt_set_sample_route: 0 (by the crossover), 1 (panel kernel) or 2 (run-time-k kernel)");
+    K->sample_route = route;
+    API_END
+}
+
+int cpk_kkt_sample_route_info(cpk_kkt K, int64_t info[4]) {
+    API_BEGIN
+    need(K && info, "NULL argument");
+    const int64_t v[4] = {kMultiKP, kSamplePanelMaxPad, K->sample_route, K->sample_panels};
+    std::memcpy(info, v, sizeof v);
+    API_END
+}
+
+int cpk_kkt_sample_multi_device(cpk_kkt K, int64_t k, const double *d_X, int64_t ldx, const double *d_Lam, int64_t ldl,
+                                double *d_gA, int64_t cA, double *d_gB, int64_t cB, double *d_gC, int64_t cC) {
+    API_BEGIN
+    check_kkt_sample(K, k, d_X, ldx, d_Lam, ldl, d_gA, cA, d_gB, cB, d_gC, cC);
+    kkt_sample_core(K, k, d_X, ldx, d_Lam, ldl, d_gA, d_gB, d_gC);
+    CPK_HIP(hipStreamSynchronize(K->ctx->c.stream));  // the gradients are the caller's
+    API_END
+}
+
+// the gradient arrays of a host entry on the device, and back
+struct HostGrads {
+    DBuf<double> d[3];
+    double *h[3];
+    int64_t cnt[3];
+    HostGrads(double *gA, int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC) : h{gA, gB, gC}, cnt{cA, cB, cC} {
+        for (int i = 0; i < 3; i++)
+            if (h[i]) d[i].alloc((size_t)std::max<int64_t>(cnt[i], 1));
+    }
+    double *dev(int i) { return h[i] ? d[i].p : nullptr; }
+    void down(Ctx &c) {
+        for (int i = 0; i < 3; i++)
+            if (h[i] && cnt[i])
+                CPK_HIP(hipMemcpyAsync(h[i], d[i].p, (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+    }
+};
+
+int cpk_kkt_sample_multi(cpk_kkt K, int64_t k, const double *X, int64_t ldx, const double *Lam, int64_t ldl, double *gA,
+                         int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC) {
+    API_BEGIN
+    check_kkt_sample(K, k, X, ldx, Lam, ldl, gA, cA, gB, cB, gC, cC);
+    const int64_t N = K->n + K->m;
+    HostBlock dX(N, std::max<int64_t>(k, 1)), dL(N, std::max<int64_t>(k, 1));
+    dX.k = dL.k = k;
+    if (k) dX.up(X, ldx), dL.up(Lam, ldl);
+    HostGrads g(gA, cA, gB, cB, gC, cC);
+    kkt_sample_core(K, k, dX.d.p, dX.ld(), dL.d.p, dL.ld(), g.dev(0), g.dev(1), g.dev(2));
+    g.down(K->ctx->c);
+    API_END
+}
+
+// Lam = cpk_kkt_solve_multi(K, GX), then cpk_kkt_sample_multi(K, X, Lam).  A column whose driver
+// stopped returns its status before any gradient pass is enqueued (the single-column rule)
+static void check_kkt_adjoint_multi(cpk_kkt K, int method, int64_t k, const double *X, int64_t ldx, const double *GX,
+                                    int64_t ldg, cpk_pc M, const double *Lam, int64_t ldl, const double *gA, int64_t cA,
+                                    const double *gB, int64_t cB, const double *gC, int64_t cC) {
+    need(K && M && ((X && GX && Lam) || !(K->n + K->m)), "NULL argument");
+    check_kkt_sample(K, k, X, ldx, Lam, ldl, gA, cA, gB, cB, gC, cC);
+    check_kkt_solve_multi(K, method, k, GX, ldg, M, Lam, ldl);
+}
+
+int cpk_kkt_adjoint_multi_device(cpk_kkt K, int method, int64_t k, const double *d_X, int64_t ldx, const double *d_GX,
+                                 int64_t ldg, cpk_pc M, const cpk_opts *opts, double *d_Lam, int64_t ldl, int warm,
+                                 double *d_gA, int64_t cA, double *d_gB, int64_t cB, double *d_gC, int64_t cC,
+                                 cpk_stats *stats, int *col_status, double *res) {
+    API_BEGIN
+    check_kkt_adjoint_multi(K, method, k, d_X, ldx, d_GX, ldg, M, d_Lam, ldl, d_gA, cA, d_gB, cB, d_gC, cC);
+    std::string msg;
+    const int rc = kkt_solve_multi_core(K, method, k, d_GX, ldg, M, opts, d_Lam, ldl, warm, stats, col_status, res, &msg);
+    if (rc != CPK_OK) return solve_multi_result(rc, msg);
+    kkt_sample_core(K, k, d_X, ldx, d_Lam, ldl, d_gA, d_gB, d_gC);
+    CPK_HIP(hipStreamSynchronize(K->ctx->c.stream));
+    API_END
+}
+
+int cpk_kkt_adjoint_multi(cpk_kkt K, int method, int64_t k, const double *X, int64_t ldx, const double *GX, int64_t ldg,
+                          cpk_pc M, const cpk_opts *opts, double *Lam, int64_t ldl, int warm, double *gA, int64_t cA,
+                          double *gB, int64_t cB, double *gC, int64_t cC, cpk_stats *stats, int *col_status, double *res) {
+    API_BEGIN
+    check_kkt_adjoint_multi(K, method, k, X, ldx, GX, ldg, M, Lam, ldl, gA, cA, gB, cB, gC, cC);
+    const int64_t N = K->n + K->m, k1 = std::max<int64_t>(k, 1);
+    HostBlock dX(N, k1), dG(N, k1), dL(N, k1);
+    dX.k = dG.k = dL.k = k;
+    if (k) dX.up(X, ldx), dG.up(GX, ldg);
+    if (k && warm) dL.up(Lam, ldl);
+    HostGrads g(gA, cA, gB, cB, gC, cC);
+    std::string msg;
+    const int rc = kkt_solve_multi_core(K, method, k, dG.d.p, dG.ld(), M, opts, dL.d.p, dL.ld(), warm, stats, col_status, res,
+                                        &msg);
+    if (k) dL.down(Lam, ldl);
+    if (rc != CPK_OK) return solve_multi_result(rc, msg);
+    kkt_sample_core(K, k, dX.d.p, dX.ld(), dL.d.p, dL.ld(), g.dev(0), g.dev(1), g.dev(2));
+    g.down(K->ctx->c);
     API_END
 }
 

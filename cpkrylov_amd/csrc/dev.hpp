@@ -307,6 +307,30 @@ constexpr int kApplyMultiMinCols = 7;
 // 0.210 ms for 8), so no such k exists yet and the constant is above a full panel: the entry routes
 // every panel to the loop, and the panel path runs where cpk_kkt_set_route forces it
 constexpr int kKktPanelMinCols = kMultiKP + 1;
+// The block adjoint's gradient passes (adjoint.hip, cpk_kkt_sample_multi).  Interleaved panels:
+// PX[(p * N + i) * kMultiKP + c] = X[i + (kMultiKP * p + c) * ldx], PL the same from L, the columns
+// beyond k of the last panel +0.0; PX and PL hold panel_count(k) * N * kMultiKP doubles each
+inline int64_t panel_count(int64_t k) { return (k + kMultiKP - 1) / kMultiKP; }
+void launch_pack_panels(Ctx &c, int64_t N, int64_t k, const double *X, int64_t ldx, const double *L, int64_t ldl,
+                        double *PX, double *PL);
+// g_q = alpha * sum_{c < k} (U1_c[i] * V1_c[j], then with U2: + U2_c[i] * V2_c[j]) for every stored
+// entry q = (i, j) of A, from 0.0 in column order without FMA, through A's value map as
+// launch_sample_outer writes it.  U*, V*: interleaved panels (row i's group at 8 i doubles, panel p
+// at p * pstride doubles); U2 == V2 == nullptr: one product per column.  Bit-equal to
+// launch_sample_outer on the same columns (for U2: on the 2k columns [U1_0, U2_0, ...], [V1_0, V2_0, ...])
+void launch_sample_panel(Ctx &c, const DMat &A, const ValueMap &vm, const DValueMap &dm, int64_t k, int64_t pstride,
+                         const double *U1, const double *V1, const double *U2, const double *V2, double alpha,
+                         double *out);
+// cpk_kkt_sample_multi's measured rule (profiles/adjoint_multi_timing.json, DESIGN.md "The block
+// adjoint").  The panel path costs the same for every k of a panel count -- the transposing pass
+// writes whole panels -- and the other path (launch_sample_outer on the column-major blocks, gB's 2k
+// columns staged) grows with k, so the panel path wins where its last panel is full: the three
+// gradients of one call in every round on both measured systems at k = 8, 16 and 24 (at S10 +-4
+// 1.13 against 1.18 ms for 8), and at no measured k with padded columns at S10 +-4 (k = 7: 1.11
+// against 1.03 ms; k = 15: 2.17 against 2.16 ms).  So the entry takes the panel path when at most
+// this many columns of the last panel are padding, and cpk_kkt_set_sample_route forces either path
+constexpr int kSamplePanelMaxPad = 0;
+inline bool sample_panel_rule(int64_t k) { return k >= 2 && panel_count(k) * kMultiKP - k <= kSamplePanelMaxPad; }
 struct MultiPlan {
     bool ready = false;
     std::vector<size_t> lds;

@@ -632,6 +632,66 @@ int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *B, int
 int cpk_reg_solve_multi_device(cpk_ctx ctx, int method, int64_t k, const double *d_B, int64_t ldb, cpk_mat A,
                                cpk_mat Bm, cpk_mat C, cpk_pc M, const cpk_opts *opts, double *d_X, int64_t ldx,
                                cpk_stats *stats, int *col_status);
+/* The block forms of cpk_kkt_solve and cpk_kkt_adjoint: N x k column-major blocks with leading
+ * dimensions >= N, as cpk_kkt_residual takes them; host arrays, or (_device) device arrays.
+ *
+ * cpk_kkt_solve_multi: column j is cpk_kkt_solve on B(:, j).  warm == 0: X(:, j) = 0 and the start
+ * sums are those of b_j.  warm != 0 (one flag for the block): X holds X0 on entry, R = B - K*X0 by
+ * the block residual, the driver runs on R and X = X0 + dX per column -- EVERY COLUMN'S STOP TEST THEN
+ * RUNS ON ITS CORRECTION SYSTEM, as in cpk_kkt_solve.  The driver is cpk_reg_solve_multi_device
+ * unchanged: CPK_CG and CPK_MINRES (any other method: CPK_ERR_UNSUPPORTED), never routed by k, so a
+ * column's bits do not depend on k, on its position or on its neighbours.  stats: k entries or NULL;
+ * col_status: k cpk_status values or NULL; res (HOST memory in both variants, 8 k doubles, may be
+ * NULL): res[8 j .. 8 j + 7] are column j's eight sums in cpk_kkt_solve's layout, the last four from
+ * one block residual of the returned X.  Errors are per column as in cpk_method_solve_multi: the
+ * return value is the first failing column's status, col_status holds all of them, and every
+ * column's X and sums are still written.  Refused before anything is written: NULL arguments
+ * (CPK_ERR_ARGS), k < 0 or a leading dimension below N (CPK_ERR_DIM), and what
+ * cpk_method_solve_multi refuses with CPK_ERR_UNSUPPORTED (a distributed context among them).
+ * k == 0 does nothing.  K keeps the block workspace, grown on first use. */
+int cpk_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double *B, int64_t ldb, cpk_pc M, const cpk_opts *opts,
+                        double *X, int64_t ldx, int warm, cpk_stats *stats, int *col_status, double *res);
+int cpk_kkt_solve_multi_device(cpk_kkt K, int method, int64_t k, const double *d_B, int64_t ldb, cpk_pc M,
+                               const cpk_opts *opts, double *d_X, int64_t ldx, int warm, cpk_stats *stats,
+                               int *col_status, double *res);
+/* The three gradient passes alone, from a block X and a block Lam (x_c = [xx_c; xy_c], lam_c =
+ * [lx_c; ly_c]), each gradient in its handle's creating call's value order; a NULL gradient is not
+ * formed, a count must be its handle's entry count (CPK_ERR_DIM).  Per stored entry (i, j) the sum
+ * starts at 0.0 and adds separately rounded products (no FMA) in column order c = 0 ... k-1, the
+ * factor applied last with one rounding:
+ *     gA = -1 * sum_c lx_c[i] * xx_c[j]
+ *     gB = -1 * sum_c (ly_c[i] * xx_c[j], then xy_c[i] * lx_c[j])
+ *     gC = +1 * sum_c ly_c[i] * xy_c[j]
+ * -- cpk_mat_sample_outer's sums on the stacked columns (for gB the 2k columns [ly_0, xy_0, ...] and
+ * [xx_0, lx_0, ...]), and with k == 1 cpk_kkt_adjoint's bits.  Every entry of each creating call
+ * is written exactly once; k == 0 writes factor * 0.0.  The call returns when the gradients are
+ * complete.  A distributed context: CPK_ERR_UNSUPPORTED. */
+int cpk_kkt_sample_multi(cpk_kkt K, int64_t k, const double *X, int64_t ldx, const double *Lam, int64_t ldl, double *gA,
+                         int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC);
+int cpk_kkt_sample_multi_device(cpk_kkt K, int64_t k, const double *d_X, int64_t ldx, const double *d_Lam, int64_t ldl,
+                                double *d_gA, int64_t cA, double *d_gB, int64_t cB, double *d_gC, int64_t cC);
+/* The sampler has two paths with the same bits: the run-time-k kernel of cpk_mat_sample_outer on the
+ * column-major blocks (for gB on 2k staged columns), and a panel kernel on interleaved copies of X
+ * and Lam (8 columns of a row contiguous).  cpk_kkt_set_sample_route: 0 by the measured rule
+ * (default: the panel kernel where the last panel is full, DESIGN.md "The block adjoint"), 1 always
+ * the panel kernel (k >= 2), 2 always the run-time-k kernel (tests, measurements).
+ * cpk_kkt_sample_route_info: {columns per panel, the padded columns of the last panel up to which
+ * the rule takes the panel kernel, the route, the calls that took the panel kernel so far}. */
+int cpk_kkt_set_sample_route(cpk_kkt K, int route);
+int cpk_kkt_sample_route_info(cpk_kkt K, int64_t info[4]);
+/* Lam = cpk_kkt_solve_multi(K, method, GX, M, opts, warm), then cpk_kkt_sample_multi(K, X, Lam): the
+ * gradients of a batch, summed over its k columns in one pass per handle.  There is no KT: the block
+ * methods are the symmetric ones, BY WHICH THE CALLER ASSERTS THAT A IS SYMMETRIC (not checked).
+ * If any column's driver stops with an error the call returns that status (col_status names the
+ * columns) before any gradient pass is enqueued: Lam and res are written, no gradient array is
+ * touched.  Refusals are those of the two entries, before anything is written. */
+int cpk_kkt_adjoint_multi(cpk_kkt K, int method, int64_t k, const double *X, int64_t ldx, const double *GX, int64_t ldg,
+                          cpk_pc M, const cpk_opts *opts, double *Lam, int64_t ldl, int warm, double *gA, int64_t cA,
+                          double *gB, int64_t cB, double *gC, int64_t cC, cpk_stats *stats, int *col_status, double *res);
+int cpk_kkt_adjoint_multi_device(cpk_kkt K, int method, int64_t k, const double *d_X, int64_t ldx, const double *d_GX,
+                                 int64_t ldg, cpk_pc M, const cpk_opts *opts, double *d_Lam, int64_t ldl, int warm,
+                                 double *d_gA, int64_t cA, double *d_gB, int64_t cB, double *d_gC, int64_t cC,
+                                 cpk_stats *stats, int *col_status, double *res);
 /* Diagnostic (not in the reference): the block solve's Krylov product alone.  Y(:, j) =
  * blkdiag(A, C) * X(:, j), equal to cpk_mat_spmv on the column bit for bit, and dots[2 j],
  * dots[2 j + 1] = <y_j(1:n), x_j(1:n)>, <y_j(n+1:N), x_j(n+1:N)> as the solvers take them (the
