@@ -158,6 +158,9 @@ struct SolveDriver {
     int batch = 16;
     bool use_graph = true;
     bool single_step = false;  // every batch is one iteration (an operator-valued A called eagerly)
+    // the iterations after which the device ends a loop by itself: itmax, except in a cpgmres cycle,
+    // which counts from 0 to restart whatever itmax is (cpgmres.m:203) -- run_batches' guard
+    double loop_limit = 0;
     GraphCache graphs;
     DBuf<DState> dst;     // a state per column: nstates travel between host and device,
     DState hs[kMultiKP];  // the first kc of a call are live
@@ -172,6 +175,7 @@ struct SolveDriver {
             if (o->has_btol) btol = o->btol;
             if (o->has_itmax) itmax = o->itmax;
         }
+        loop_limit = itmax;
         use_graph = !c.opts.no_graph;
         single_step = false;
         batch = c.opts.batch > 0 ? c.opts.batch : 16;
@@ -200,7 +204,7 @@ struct SolveDriver {
     // live column's `stop`; the host only reads the states back between batches.
     // around(launch, readback): what surrounds a batch; it calls both, in that order (SolveCore: the
     // distributed status agreement).  printer (optional): called after every read-back.
-    // The loop fails when a column runs itmax + 2 batches past its iteration count at entry.
+    // The loop fails when a column runs loop_limit + 2 batches past its iteration count at entry.
     template <class Batch = PlainBatch>
     void run_batches(size_t site, int kc, int64_t &inst, const std::function<void()> &body,
                      const Batch &around = Batch(), const std::function<void()> &printer = nullptr) {
@@ -208,7 +212,7 @@ struct SolveDriver {
         if (stopped(kc)) return;
         int64_t guard = 0;
         for (int j = 0; j < kc; j++) guard = std::max(guard, hs[j].k);
-        guard += (int64_t)std::min(itmax, 4.0e9) + 2 * batch + 2;
+        guard += (int64_t)std::min(loop_limit, 4.0e9) + 2 * batch + 2;
         BatchPlan plan{single_step ? 1 : pow2_at_least(batch, 64), c.opts.batch <= 0, itmax};
         int b = plan.base;
         for (;;) {

@@ -1956,9 +1956,17 @@ void SolveCore::cg(const double *b, double *xy, cpk_stats *stats) {
 void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
     const int64_t R = (int64_t)restart;
     if (R < 1) throw Error(CPK_ERR_ARGS, "restart must be >= 1");
+    // outermax = ceil(itmax/restart) < 1 (cpgmres.m:148): the outer loop never runs and the wrap-up
+    // references k before assignment: MATLAB errors there, and nothing has looked at the residual
+    if (!(std::ceil(itmax / (double)R) >= 1)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "Undefined variable k (itmax = %g: the outer loop never runs, cpgmres.m:267)", itmax);
+        throw Error(CPK_ERR_ARGS, buf);
+    }
     // the cycles can overrun itmax by up to restart-1 iterations (cpgmres.m:148,203)
     const int64_t hcap = (int64_t)(std::ceil(std::min(itmax, 1.0e8) / (double)R) * R) + 4;
     setup_state(hcap, R);
+    loop_limit = std::max((double)R, itmax);  // a cycle runs to restart, past a smaller itmax (cpgmres.m:203)
     DState *st = dst.p;
     double *V = ring((size_t)(R + 1));
     double *UT = vec(0), *Wv = vec(1), *TMP = vec(2);

@@ -426,7 +426,8 @@ int cpk_plan_destroy(cpk_plan plan);
 
 /* ---- solvers --------------------------------------------------------------------------- */
 /* [x, y, stats, flag] = method(b, A, C, M, opts)   (kernels/cp*.m, e.g. cpminres.m:1).
- * b: n, x: n, y: m (host). */
+ * b: n, x: n, y: m (host).  CPK_GMRES with ceil(itmax/restart) < 1 (itmax <= 0) is CPK_ERR_ARGS:
+ * the reference's outer loop never runs and cpgmres.m:267 reads a k that was never assigned. */
 int cpk_method_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_mat C, cpk_pc M,
                      const cpk_opts *opts, double *x, double *y, cpk_stats *stats);
 /* Same with device-resident b (n) and xy (N = [x; y]); nothing crosses PCIe except the

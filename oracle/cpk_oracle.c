@@ -973,6 +973,10 @@ static int run_gmres(int64_t n, int64_t m, const double *b, const orc_csr *A, co
     int64_t N = n + m;
     int64_t restart = (int64_t)s.restart;
     if (restart < 1) return set_err(ORC_ERR_ARGS, "restart must be >= 1");
+    /* outermax = ceil(itmax/restart) < 1 (cpgmres.m:148): the outer loop never runs and the wrap-up
+     * references k before assignment: MATLAB errors there, and nothing has looked at the residual */
+    if (!(ceil(s.itmax / (double)restart) >= 1))
+        return set_err(ORC_ERR_ARGS, "Undefined variable k (itmax = %g: the outer loop never runs, cpgmres.m:267)", s.itmax);
     int64_t R1 = restart + 1;
     double *g = calloc((size_t)R1, sizeof(double));
     double *V = calloc((size_t)(n * R1 > 0 ? n * R1 : 1), sizeof(double));

@@ -223,6 +223,17 @@ def _run(fn, method, hist_cap, *args):
     return stats, st
 
 
+def _hist_cap(name, opts, default_itmax):
+    """Default history capacity: itmax entries and the initial ones; cpgmres's cycles can overrun
+    itmax by up to restart-1 iterations (cpgmres.m:148,203), so its itmax rounds up to a multiple
+    of restart (as the product's api._hist_cap)."""
+    itmax = max(int(np.ceil((opts or {}).get("itmax", default_itmax))), 0)
+    if name == "gmres":
+        r = max(int((opts or {}).get("restart", 50)), 1)
+        itmax = -(-itmax // r) * r
+    return itmax + 3
+
+
 def method(name, b, A, Cm, M, opts=None, hist_cap=None):
     """[x, y, stats, flag] = cp<name>(b, A, C, M, opts)"""
     n, m = A.shape[0], Cm.shape[0]
@@ -230,7 +241,7 @@ def method(name, b, A, Cm, M, opts=None, hist_cap=None):
     hA, hC = _CsrHold(A), _CsrHold(Cm)
     o = _opts(opts)
     x, y = np.zeros(n), np.zeros(m)
-    cap = hist_cap or int((opts or {}).get("itmax", n + m)) + 3
+    cap = hist_cap or _hist_cap(name, opts, n + m)
     stats, _ = _run(lambda mid, *rest: lib().orc_method(mid, _ptr(b, C.c_double), C.byref(hA.s), C.byref(hC.s),
                                                         M.h, C.byref(o), *rest),
                     name, cap, _ptr(x, C.c_double), _ptr(y, C.c_double))
@@ -249,7 +260,7 @@ def reg_cpkrylov(name, b, A, B, Cm, G, opts=None, order="rcm", perm=None, hist_c
         perm = np.ascontiguousarray(perm, np.int32)
         pp = _ptr(perm, C.c_int32)
         order = "given"
-    cap = hist_cap or int((opts or {}).get("itmax", n + m)) + 3
+    cap = hist_cap or _hist_cap(name, opts, n + m)
     stats, st = _run(lambda mid, xp, stp: lib().orc_reg_cpkrylov(
         mid, _ptr(b, C.c_double), *[C.byref(h.s) for h in hs], C.byref(o), ORDER[order], pp, xp, stp, None),
         name, cap, _ptr(x, C.c_double))
@@ -265,7 +276,7 @@ def reg_solve(name, b, A, B, Cm, M, opts=None, hist_cap=None):
     hs = [_CsrHold(X) for X in (A, B, Cm)]
     o = _opts(opts)
     x = np.zeros(n + m)
-    cap = hist_cap or int((opts or {}).get("itmax", n + m)) + 3
+    cap = hist_cap or _hist_cap(name, opts, n + m)
     stats, st = _run(lambda mid, xp, stp: lib().orc_reg_solve(
         mid, _ptr(b, C.c_double), *[C.byref(h.s) for h in hs], M.h, C.byref(o), xp, stp),
         name, cap, _ptr(x, C.c_double))
