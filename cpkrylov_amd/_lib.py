@@ -59,6 +59,16 @@ class Profile(C.Structure):
                [("fwd_resid_ms", C.c_double), ("fwd_resid_bytes", C.c_double), ("bwd_dead_store_bytes", C.c_double)]
 
 
+class ArnoldiStep(C.Structure):
+    """cpk_arnoldi_step: one Arnoldi step of cpgmres / cpdqgmres on the caller's data (diagnostic)."""
+    _fields_ = [(k, C.c_int) for k in ("method", "running", "grid")] + \
+               [(k, C.c_int64) for k in ("n", "N", "win", "kk", "itmax")] + \
+               [(k, C.c_double) for k in ("stopTol", "residNorm", "hk1", "hist")] + \
+               [("V", C.POINTER(C.c_double)), ("ldv", C.c_int64), ("PV", C.POINTER(C.c_double)), ("ldpv", C.c_int64)] + \
+               [(k, C.POINTER(C.c_double)) for k in ("xy", "w", "ut", "H", "c", "s", "g", "H_dots")] + \
+               [("stop", C.c_int), ("err", C.c_int), ("err_val", C.c_double), ("err_iter", C.c_int64), ("nh", C.c_int64)]
+
+
 P = C.POINTER
 vp = C.c_void_p
 # cpk_op_fn: int fn(void *user, const double *d_x, double *d_y, int64_t n, void *stream)
@@ -189,6 +199,7 @@ _SIGS = {
     "cpk_debug_dot": ([vp, C.c_int, C.c_int64, C.c_int, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, C.c_int,
                        P(C.c_double)], C.c_int),
     "cpk_debug_xnorm2": ([vp, C.c_int64, P(C.c_double), P(C.c_double), P(C.c_double)], C.c_int),
+    "cpk_debug_arnoldi_step": ([vp, P(ArnoldiStep)], C.c_int),
     "cpk_debug_spmm_time": ([vp, vp, vp, vp, C.c_int, C.c_int, P(C.c_double), P(C.c_double)], C.c_int),
     "cpk_reg_shift_device": ([vp, vp, vp, vp, vp, vp, vp, vp, P(C.c_int)], C.c_int),
     "cpk_profile_kernels": ([vp, vp, vp, vp, C.c_int, P(Profile)], C.c_int),

@@ -1856,6 +1856,30 @@ int cpk_debug_xnorm2(cpk_ctx ctx, int64_t n, const double *a, const double *b, d
     API_END
 }
 
+// diagnostic: one Arnoldi step of cpgmres / cpdqgmres on host arrays, through the solvers' launches
+int cpk_debug_arnoldi_step(cpk_ctx ctx, cpk_arnoldi_step *io) {
+    API_BEGIN
+    need(ctx && io, "NULL argument");
+    cpk_arnoldi_step &s = *io;
+    const bool dq = s.method == CPK_DQGMRES;
+    need(dq || s.method == CPK_GMRES, "debug_arnoldi_step: method is CPK_GMRES or CPK_DQGMRES");
+    need(s.V && s.w && s.ut && s.H && s.c && s.s && s.g, "NULL argument");
+    need(!dq || (s.PV && s.xy), "debug_arnoldi_step: cpdqgmres needs PV and xy");
+    need(s.N >= 0 && s.n >= 0 && s.n <= s.N, "debug_arnoldi_step: 0 <= n <= N required");
+    need(s.win >= 1 && s.win <= (int64_t)1 << 20, "debug_arnoldi_step: 1 <= restart, mem <= 2^20 required");
+    need(s.kk >= 1 && (dq || s.kk <= s.win), "debug_arnoldi_step: kk >= 1 (cpgmres: kk <= restart) required");
+    need(s.grid >= 0, "debug_arnoldi_step: grid >= 0 required");
+    need(s.ldv >= s.N && (!dq || s.ldpv >= s.N), "debug_arnoldi_step: leading dimensions >= N required");
+    const int64_t N = s.N, cols = s.win + 1;
+    HostBlock dV(N, cols), dPV(N, dq ? cols : 1), dxy(N, 1), dw(N, 1), dut(N, 1);
+    dV.up(s.V, s.ldv), dw.up(s.w, N), dut.up(s.ut, N);
+    if (dq) dPV.up(s.PV, s.ldpv), dxy.up(s.xy, N);
+    debug_arnoldi_step(ctx->c, s, dV.d.p, dPV.d.p, dxy.d.p, dw.d.p, dut.d.p);
+    dV.down(s.V, s.ldv);
+    if (dq) dPV.down(s.PV, s.ldpv), dxy.down(s.xy, N);
+    API_END
+}
+
 int cpk_debug_spmm_time(cpk_ctx ctx, cpk_mat A, cpk_mat C, cpk_pc M, int kc, int reps, double *ms_panel, double *ms_single) {
     API_BEGIN
     need(ctx && A && C && M && ms_panel && ms_single, "NULL argument");

@@ -1208,8 +1208,9 @@ __global__ void arnoldi_fin_kernel(DState *st, int64_t ring, const double *tot) 
 }
 
 // the window dots of one Arnoldi step (with the distributed allreduce when needed)
+// grid_override: 0 for the solvers' own grid; cpk_debug_arnoldi_step passes another one (<= kEwGrid)
 static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, const double *ut, int64_t n, int64_t N,
-                                int64_t ring, int64_t maxv) {
+                                int64_t ring, int64_t maxv, int grid_override = 0) {
     const bool dist = c.dist();
     if (dist && (size_t)(2 * maxv) > c.red.n) throw Error(CPK_ERR_UNSUPPORTED, "Arnoldi window too wide for the distributed reduction buffer");
     // at most the resident workgroups (occupancy x CUs): a trailing partial wave of workgroups
@@ -1223,7 +1224,7 @@ static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, 
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         return occ * cus;
     }();
-    const int grid = std::min(ew_grid(N), resident);
+    const int grid = grid_override > 0 ? std::min(grid_override, kEwGrid) : std::min(ew_grid(N), resident);
     if (c.exact())
         hipLaunchKernelGGL(arnoldi_dots_exact_kernel, dim3(grid), dim3(kBlock), 0, c.stream, st, V, w, ut, n, N, ring,
                            maxv, red_buf(c));
@@ -1523,6 +1524,27 @@ struct Copy {
 // ==============================================================================================
 // host driver
 // ==============================================================================================
+// The sizes of an Arnoldi solver's small state (doubles): H as Hg / Hd index it, the rotations,
+// g and the back substitution's z.  SolveCore::setup_state and cpk_debug_arnoldi_step both size from here.
+struct ArnoldiSizes {
+    size_t H, c, s, g, z;
+};
+static ArnoldiSizes arnoldi_sizes(int method, int64_t R, int64_t Mm) {
+    if (method == CPK_GMRES) return {(size_t)((R + 1) * R), (size_t)R, (size_t)R, (size_t)(R + 1), (size_t)R};
+    return {(size_t)((Mm + 2) * (Mm + 2)), (size_t)Mm, (size_t)Mm, (size_t)(Mm + 1), (size_t)1};
+}
+// The context's reduction workspace for a solve on N-vectors with Arnoldi windows of up to maxv
+// vectors (0: none): a partial per workgroup, sum and window vector (at least op_partials, what the
+// operators' own reductions take), and in exact mode a sub-accumulator set per sum.
+static void size_reductions(Ctx &c, size_t op_partials, int64_t N, int64_t maxv) {
+    size_t need = op_partials;
+    const size_t ewg = (size_t)std::max<int64_t>(kEwGrid, ewt_grid(N));
+    need = std::max<size_t>(need, ewg * 2);
+    need = std::max<size_t>(need, ewg * 2 * std::max<int64_t>(maxv, 1));
+    c.ensure_partials(need);
+    if (c.exact()) c.ensure_xacc((size_t)std::max<int64_t>(2 * maxv, 4));
+}
+
 // A SolveCore is kept by the preconditioner between calls with the same method, operators,
 // vectors and captured properties (solver_key): its workspace and the captured iteration
 // graphs are reused, so a repeated solve costs its kernels plus one state upload.
@@ -1603,24 +1625,13 @@ struct SolveCore : SolveDriver {
         h.restart = (int64_t)restart;
         h.mem = (int64_t)mem;
         if (maxv > 0) {
-            const int64_t R = h.restart, Mm = h.mem;
-            if (method == CPK_GMRES) {
-                ensure(H, (R + 1) * R);
-                ensure(cvec, R), ensure(svec, R), ensure(gvec, R + 1), ensure(zvec, R);
-            } else {
-                ensure(H, (Mm + 2) * (Mm + 2));
-                ensure(cvec, Mm), ensure(svec, Mm), ensure(gvec, Mm + 1), ensure(zvec, 1);
-            }
+            const ArnoldiSizes z = arnoldi_sizes(method, h.restart, h.mem);
+            ensure(H, z.H), ensure(cvec, z.c), ensure(svec, z.s), ensure(gvec, z.g), ensure(zvec, z.z);
             H.zero(c.stream), cvec.zero(c.stream), svec.zero(c.stream), gvec.zero(c.stream);
             h.H = H.p, h.c = cvec.p, h.s = svec.p, h.g = gvec.p, h.z = zvec.p;
         }
         CPK_HIP(hipMemcpyAsync(dst.p, &h, sizeof h, hipMemcpyHostToDevice, c.stream));
-        size_t need = std::max<size_t>((size_t)AC.nblk * 2, (size_t)M.dKp.nblk * 2);
-        const size_t ewg = (size_t)std::max<int64_t>(kEwGrid, ewt_grid(N));
-        need = std::max<size_t>(need, ewg * 2);
-        need = std::max<size_t>(need, ewg * 2 * std::max<int64_t>(maxv, 1));
-        c.ensure_partials(need);
-        if (c.exact()) c.ensure_xacc((size_t)std::max<int64_t>(2 * maxv, 4));
+        size_reductions(c, std::max<size_t>((size_t)AC.nblk * 2, (size_t)M.dKp.nblk * 2), N, maxv);
     }
 
     // ---- the distributed solve's status agreement -------------------------------------------
@@ -2330,6 +2341,52 @@ void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, doubl
     launch_ew(c, n, DebugXnorm2{d_a, d_b, d_out});
     CPK_HIP(hipGetLastError());
     CPK_HIP(hipStreamSynchronize(c.stream));
+}
+
+// Diagnostic (cpk_debug_arnoldi_step): the three launches of a cpgmres / cpdqgmres iteration after
+// M.apply -- launch_arnoldi_dots, launch_ewtred<2>(ArnoldiOrth) and GmresNormalize / DqgmresDirection,
+// as gmres() and dqgmres() make them -- on a state built from the caller's values, so the window
+// kernels can be tested at window widths, ring positions and scalar branches that no solve reaches
+// (tests/test_gpu_arnoldi_step.py).  The small state and the reduction workspace are sized by
+// arnoldi_sizes / size_reductions, as setup_state sizes them.
+void debug_arnoldi_step(Ctx &c, cpk_arnoldi_step &s, double *d_V, double *d_PV, double *d_xy, const double *d_w,
+                        const double *d_ut) {
+    const bool dq = s.method == CPK_DQGMRES;
+    const int64_t N = s.N, n = s.n, maxv = s.win, ring = dq ? s.win + 1 : 0;
+    const ArnoldiSizes z = arnoldi_sizes(s.method, s.win, s.win);
+    DBuf<double> H, cv, sv, gv, zv, hist;
+    DBuf<DState> dst;
+    H.upload(s.H, z.H), cv.upload(s.c, z.c), sv.upload(s.s, z.s), gv.upload(s.g, z.g);
+    zv.alloc(z.z), hist.upload(&s.hist, 1), dst.alloc(1);
+    size_reductions(c, 0, N, maxv);
+    DState h;
+    std::memset(&h, 0, sizeof h);
+    h.k = s.kk, h.itmax = s.itmax, h.hcap = 1, h.hist = hist.p;
+    h.running = s.running ? 1 : 0;
+    h.exact = c.exact() ? 1 : 0;
+    h.stopTol = s.stopTol, h.residNorm = s.residNorm, h.hk1 = s.hk1;
+    h.restart = s.win, h.mem = s.win;
+    h.H = H.p, h.c = cv.p, h.s = sv.p, h.g = gv.p, h.z = zv.p;
+    CPK_HIP(hipMemcpy(dst.p, &h, sizeof h, hipMemcpyHostToDevice));
+    DState *st = dst.p;
+    launch_arnoldi_dots(c, st, d_V, d_w, d_ut, n, N, ring, maxv, s.grid);
+    if (s.H_dots) {
+        CPK_HIP(hipMemcpyAsync(s.H_dots, H.p, z.H * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+    }
+    launch_ewtred<2>(c, N, ArnoldiOrth{st, d_V, d_ut, n, N, ring, Window{}, nullptr});
+    if (dq) launch_ewt(c, N, DqgmresDirection{st, d_V, d_PV, d_xy, n, N});
+    else launch_ew(c, N, GmresNormalize{st, d_V, N});
+    CPK_HIP(hipGetLastError());
+    CPK_HIP(hipMemcpyAsync(&h, dst.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    CPK_HIP(hipMemcpy(s.H, H.p, z.H * sizeof(double), hipMemcpyDeviceToHost));
+    CPK_HIP(hipMemcpy(s.c, cv.p, z.c * sizeof(double), hipMemcpyDeviceToHost));
+    CPK_HIP(hipMemcpy(s.s, sv.p, z.s * sizeof(double), hipMemcpyDeviceToHost));
+    CPK_HIP(hipMemcpy(s.g, gv.p, z.g * sizeof(double), hipMemcpyDeviceToHost));
+    CPK_HIP(hipMemcpy(&s.hist, hist.p, sizeof(double), hipMemcpyDeviceToHost));
+    s.stopTol = h.stopTol, s.residNorm = h.residNorm, s.hk1 = h.hk1;
+    s.stop = h.stop, s.err = h.err, s.err_val = h.err_val, s.err_iter = h.err_iter, s.nh = h.nh;
 }
 
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out) {

@@ -74,6 +74,12 @@ void debug_spmm_time(Ctx &c, const DMat &AC, Precond &M, int kc, int reps, doubl
 void debug_dot(Ctx &c, int kind, int64_t n, int nv, const double *d_A, int64_t lda, const double *d_B, int64_t ldb,
                int grid, double *d_out);
 void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, double *d_out);
+// diagnostic (cpk_debug_arnoldi_step): one Arnoldi step of cpgmres / cpdqgmres through the solvers' own
+// launches.  s: the caller's description (its scalars are read and written, its H / c / s / g / H_dots
+// are host arrays in the engine's storage); the vectors are device arrays with leading dimension
+// max(N, 1).  Collective on a distributed context.
+void debug_arnoldi_step(Ctx &c, cpk_arnoldi_step &s, double *d_V, double *d_PV, double *d_xy, const double *d_w,
+                        const double *d_ut);
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out);
 // op: AC is blkdiag(0, C); the product's model adds the gather and the epilogue's read of fn's
 // output (24 n), cpminres runs unfused, and fn's own traffic is unknown and not counted

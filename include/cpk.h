@@ -710,6 +710,47 @@ int cpk_debug_dot(cpk_ctx ctx, int kind, int64_t n, int nv, const double *A, int
                   int64_t ldb, int grid, double *out);
 /* Diagnostic: out[i] = the exact mode's norm([a[i] b[i]]) evaluated on the device, i < n. */
 int cpk_debug_xnorm2(cpk_ctx ctx, int64_t n, const double *a, const double *b, double *out);
+/* Diagnostic (not in the reference): ONE Arnoldi step of cpgmres (cpgmres.m:212-247) or cpdqgmres
+ * (cpdqgmres.m:208-269) on the caller's data, through the launches the solvers make after w = M*[u; -t]:
+ * the window dots, the orthogonalisation with its scalar step (rotations, SymGivens, g, residNorm,
+ * stop), and the normalisation (cpgmres) or the direction update (cpdqgmres).  Host arrays; every
+ * array is uploaded, the step runs, and every array but w and ut is read back.
+ *   method   CPK_GMRES or CPK_DQGMRES;  win: restart, resp. mem (>= 1)
+ *   n, N     0 <= n <= N: rows [0, n) are the x-part, [n, N) the y-part of every vector
+ *   kk       the iteration performed (>= 1; cpgmres: <= restart);  itmax: cpdqgmres's stop
+ *   running  0: the step is a no-op and nothing changes
+ *   grid     0: the solver's own grid for the window dots; > 0: that many workgroups (capped)
+ *   V        N x (win + 1), ldv >= N: cpgmres column j - 1 holds [V(:,j); Q(:,j)], column kk is written;
+ *            cpdqgmres ring slot (j - 1) % (mem + 1), slot kk % (mem + 1) is written
+ *   PV, xy   cpdqgmres only (N x (mem + 1), ldpv >= N, and N): slot (kk - 1) % (mem + 1) and [x; y]
+ *   w, ut    N each: M*[u; -t] and [u; t]
+ *   H, c, s, g  the engine's storage.  cpgmres: H(i, j) (1-based) at H[(i - 1) + (j - 1) * (restart + 1)],
+ *            (restart + 1) * restart doubles; c, s: restart; g: restart + 1.  cpdqgmres: the reference's
+ *            H(j, col), col = 2 + k - j its diagonal-compressed column, at
+ *            H[(j % (mem + 2)) * (mem + 2) + (col - 1)], (mem + 2)^2 doubles (a ring of mem + 2 rows, row kk
+ *            cleared by the step); c, s at (j - 1) % mem: mem; g at (j - 1) % (mem + 1): mem + 1.
+ *   H_dots   optional: H's storage as the window dots left it, before the orthogonalisation reads it
+ *   stopTol, residNorm, hk1, hist  in and out (hist: the one history value, written iff nh = 1)
+ *   stop, err, err_val, err_iter, nh  out (err = 4: the squared norm err_val of the new vector is negative)
+ * On a context of several ranks the call is collective: every rank passes its local rows and its
+ * own n, and receives the same scalars.  A window wider than the distributed reduction buffer
+ * (2 win sums > 4096): CPK_ERR_UNSUPPORTED.  Bad arguments: CPK_ERR_ARGS, before any device call. */
+typedef struct {
+    int method, running, grid;
+    int64_t n, N, win, kk, itmax;
+    double stopTol, residNorm, hk1, hist;
+    double *V;
+    int64_t ldv;
+    double *PV;
+    int64_t ldpv;
+    double *xy;
+    const double *w, *ut;
+    double *H, *c, *s, *g, *H_dots;
+    int stop, err;
+    double err_val;
+    int64_t err_iter, nh;
+} cpk_arnoldi_step;
+int cpk_debug_arnoldi_step(cpk_ctx ctx, cpk_arnoldi_step *io);
 
 /* Diagnostic: device time per launch (ms, HIP events, `reps` launches after a warm-up) of the
  * panel product with kc <= 8 columns and, in the same run, of the single-column Krylov product

@@ -9,10 +9,10 @@ merges of block_deposit and wave_hand, gather_digits, xround, xround_kernel behi
 allreduce, and xnorm2.  Inputs and references: xacc_cases.py (reference A: rational arithmetic,
 where no product under- or overflows; reference B: the oracle, bit for bit, always).
 
-Out of scope: arnoldi_dots_exact_kernel cannot be driven without a solve, so its own index
-arithmetic (% nsum, chunks of 16) stays covered only by the exact GMRES / DQGMRES solves
-(test_gpu_exact.py); the pieces it shares with the rest (XAcc::add, block_deposit, gather_digits,
-xround) are covered here.
+Out of scope here: arnoldi_dots_exact_kernel and its own index arithmetic (% nsum, groups of 4,
+chunks of 16).  test_gpu_arnoldi_step.py drives it, and the rest of the Arnoldi step, directly
+(cpk_debug_arnoldi_step), with these families in its window sums; the pieces it shares with the
+rest (XAcc::add, block_deposit, gather_digits, xround) are covered here.
 
 Found by this module (the values before the fix): finite terms whose partial sum overflowed in a
 thread or a merge step (H + H with H = 1.7e308) went through the TwoSum as inf - inf and the sum

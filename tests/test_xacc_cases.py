@@ -1,5 +1,5 @@
 """The exact-dot test inputs (xacc_cases.py) against the oracle and exact rational arithmetic, and
-the argument checks of cpk_debug_dot / cpk_debug_xnorm2 -- all without a device.
+the argument checks of cpk_debug_dot / cpk_debug_xnorm2 / cpk_debug_arnoldi_step -- all without a device.
 
 Every family goes through the oracle's exact inner product (orc_xdot) and is compared with the
 correctly rounded rational sum wherever that is the definition (no product under- or overflows):
@@ -140,3 +140,23 @@ def test_debug_entries_refuse_bad_arguments():
                  (h, -1, pa, pb, po)):
         assert L.cpk_debug_xnorm2(*args) == _lib.CPK_ERR_ARGS
     assert np.all(a == 1.0) and np.all(b == 2.0) and np.all(out == 7.0)  # nothing written
+    # cpk_debug_arnoldi_step: N = 4, n = 2, restart / mem = 2; V, PV: 4 x 3; H: 16 fits both layouts
+    assert hasattr(L, "cpk_debug_arnoldi_step") and "cpk_debug_arnoldi_step" in _lib.EXPORTED
+    arrs = {k: np.full(sz, 3.0) for k, sz in (("V", 12), ("PV", 12), ("xy", 4), ("w", 4), ("ut", 4), ("H", 16), ("c", 2),
+                                              ("s", 2), ("g", 3), ("H_dots", 16))}
+    GM, DQ = _lib.METHODS["gmres"], _lib.METHODS["dqgmres"]
+    ok = dict(method=DQ, running=1, grid=0, n=2, N=4, win=2, kk=2, itmax=10, stopTol=1.0, residNorm=2.0, hk1=5.0,
+              hist=6.0, ldv=4, ldpv=4, stop=-3, err=-3, err_val=-3.0, err_iter=-3, nh=-3,
+              **{k: v.ctypes.data_as(PD) for k, v in arrs.items()})
+    bad = [dict(method=0), dict(method=6), dict(V=None), dict(w=None), dict(ut=None), dict(H=None), dict(c=None),
+           dict(s=None), dict(g=None), dict(PV=None), dict(xy=None), dict(N=-1), dict(n=-1), dict(n=5), dict(kk=0),
+           dict(kk=-1), dict(win=0), dict(win=-1), dict(grid=-1), dict(ldv=3), dict(ldpv=3),
+           dict(method=GM, kk=3), dict(method=GM, win=0, kk=1), dict(method=GM, ldv=3), dict(method=GM, V=None)]
+    for d in bad:
+        io = _lib.ArnoldiStep(**dict(ok, **d))
+        assert L.cpk_debug_arnoldi_step(h, C.byref(io)) == _lib.CPK_ERR_ARGS, d
+        assert L.cpk_last_error()
+        assert (io.stop, io.err, io.err_val, io.err_iter, io.nh, io.hk1, io.hist) == (-3, -3, -3.0, -3, -3, 5.0, 6.0)
+    assert L.cpk_debug_arnoldi_step(None, C.byref(_lib.ArnoldiStep(**ok))) == _lib.CPK_ERR_ARGS
+    assert L.cpk_debug_arnoldi_step(h, None) == _lib.CPK_ERR_ARGS
+    assert all(np.all(v == 3.0) for v in arrs.values())  # nothing written
