@@ -165,6 +165,15 @@ _SIGS = {
     "cpk_kkt_solve": ([vp, C.c_int, P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int, P(Stats), P(C.c_double)],
                       C.c_int),
     "cpk_kkt_solve_device": ([vp, C.c_int, vp, vp, P(Opts), vp, C.c_int, P(Stats), P(C.c_double)], C.c_int),
+    "cpk_kkt_residual_exact": ([vp, C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double),
+                                C.c_int64, P(C.c_double)], C.c_int),
+    "cpk_kkt_residual_exact_device": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp], C.c_int),
+    "cpk_kkt_residual_exact_device_sums": ([vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, P(C.c_double)],
+                                           C.c_int),
+    "cpk_kkt_solve_refined": ([vp, C.c_int, P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int, C.c_int, P(Stats),
+                               P(C.c_double), P(C.c_int)], C.c_int),
+    "cpk_kkt_solve_refined_device": ([vp, C.c_int, vp, vp, P(Opts), vp, C.c_int, C.c_int, P(Stats), P(C.c_double),
+                                      P(C.c_int)], C.c_int),
     "cpk_kkt_adjoint": ([vp, vp, C.c_int, P(C.c_double), P(C.c_double), vp, P(Opts), P(C.c_double), C.c_int,
                          P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(C.c_double), C.c_int64, P(Stats),
                          P(C.c_double)], C.c_int),

@@ -1180,6 +1180,18 @@ class KKT:
         block).  rr_* and bb_* are the device's sums (exact under engine option exact_dots), rnorm
         and bnorm their roots.  Device operands: r goes to out= (which may be b itself); with
         want_r=False no r is stored and None is returned for it."""
+        return self._residual(lib.cpk_kkt_residual, lib.cpk_kkt_residual_device_sums, z, b, out, want_r)
+
+    def residual_exact(self, z, b, out=None):
+        """`residual` with the exactly rounded row sum (cpk_kkt_residual_exact): r_i is the exact sum
+        of b_i and the TwoProd pairs of -K_ie * z_col(e) over row i's stored entries, rounded once to
+        nearest even, so its own rounding error is half an ulp of r_i instead of eps * |K| |z|.  One
+        definition whatever the entry order or the grid; a non-finite term gives a NaN in its row
+        only.  Operands, blocks, out= and the returned (r, norms) are `residual`'s; the sums are
+        those `residual` would form on that r and b.  A block is a loop of single-column passes."""
+        return self._residual(lib.cpk_kkt_residual_exact, lib.cpk_kkt_residual_exact_device_sums, z, b, out, True)
+
+    def _residual(self, host_entry, device_entry, z, b, out, want_r):
         if _is_device(z) or _is_device(b):
             if not (_is_device(z) and _is_device(b)):
                 raise CpkError(_lib.CPK_ERR_ARGS, "residual: z and b must both be host arrays or both device tensors")
@@ -1195,7 +1207,7 @@ class KKT:
                 if kr != k:
                     raise CpkError(_lib.CPK_ERR_DIM, "out must have z's shape")
             nr = np.zeros(4 * max(k, 1))  # host memory: the entry copies the sums back and waits
-            check(lib.cpk_kkt_residual_device_sums(self.h, k, zp, ld, bp, ld, rp, ld, _dptr(nr)))
+            check(device_entry(self.h, k, zp, ld, bp, ld, rp, ld, _dptr(nr)))
             return (out if want_r else None), _norms_dict(nr[:4 * k], getattr(z, "ndim", 2) == 1)
         Z, vector = self._host_block(z, "z")
         Bm, _ = self._host_block(b, "b")
@@ -1204,7 +1216,7 @@ class KKT:
         k, ld = Z.shape[1], max(self.N, 1)
         R = np.zeros_like(Z, order="F") if want_r else None
         nr = np.zeros(4 * max(k, 1))
-        check(lib.cpk_kkt_residual(self.h, k, _dptr(Z), ld, _dptr(Bm), ld, _dptr(R) if want_r else None, ld, _dptr(nr)))
+        check(host_entry(self.h, k, _dptr(Z), ld, _dptr(Bm), ld, _dptr(R) if want_r else None, ld, _dptr(nr)))
         r = None if not want_r else (R[:, 0].copy() if vector else R)
         return r, _norms_dict(nr[:4 * k], vector)
 
@@ -1264,6 +1276,75 @@ class KKT:
         stats["ptime"], stats["stime"] = st.ptime, st.stime
         stats["true_resid0"] = _norms_dict(res[:4], True)
         stats["true_resid"] = _norms_dict(res[4:], True)
+        return x, stats, flag
+
+    def solve_refined(self, method, b, M, opts=None, x0=None, max_steps=3, out=None):
+        """x, stats, flag = K.solve_refined(method, b, M, opts, x0, max_steps): `solve` followed by up
+        to max_steps corrections of iterative refinement on the exactly rounded residual
+        (cpk_kkt_solve_refined).  Driver call j = 0 .. max_steps runs `solve`'s driver from zero on
+        r_j = residual_exact(x_j, b) (cold, j = 0: on b) and gives the trial x_j + dx_j: EACH
+        CALL'S STOP TEST RUNS ON ITS CORRECTION SYSTEM.  A trial whose residual's sum of squares is
+        not below r_j's is dropped and ends the loop with x_j; the last call's trial is taken
+        unchecked, so max_steps=0 with x0=None is the cold `solve`.  stats are the last driver
+        call's, with stats["refine_steps"] (the corrections in x: driver calls after the first whose
+        trial was taken; -1 when the first call's own trial was dropped and x is x0 or zero),
+        stats["resid_sums"] (one row [rr_x, rr_y, bb_x, bb_y] per residual formed: refine_steps + 1
+        rows, the residuals the taken driver calls ran on; where a trial was dropped two more, of the
+        returned x and of the dropped trial) and stats["true_resid"] as
+        `solve` sets it (the plain residual of the returned x).  Operands and out= are `solve`'s; a
+        stop inside the driver raises its error with `partial` = (x_j plus whatever the driver wrote,
+        resid_sums)."""
+        name = getattr(method, "_cpk_method", method)
+        if name not in _lib.METHODS:
+            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
+        if any(isinstance(v, Operator) for v in (b, M, x0, out)):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.solve_refined is matrix-only: K's (1,1) block is the matrix it was built on")
+        if not isinstance(M, opLDL2):
+            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        max_steps = int(max_steps)
+        if max_steps < 0:
+            raise CpkError(_lib.CPK_ERR_ARGS, "max_steps >= 0 required")
+        st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
+        res, steps = np.zeros(4 * (max_steps + 1)), C.c_int(0)
+        if _is_device(b):
+            if out is None or not _is_device(out):
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_refined on device operands: pass the result tensor as out=")
+            if x0 is not None and x0 is not out:
+                raise CpkError(_lib.CPK_ERR_ARGS, "solve_refined on device operands: x0 is out itself (x0 is updated in place)")
+            bp, kb, _ = _device_operand(b, "b", self.N)
+            xp, kx, _ = _device_operand(out, "out", self.N)
+            if kb != 1 or kx != 1:
+                raise CpkError(_lib.CPK_ERR_DIM, "solve_refined takes one right-hand side of N entries")
+            rc = lib.cpk_kkt_solve_refined_device(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp,
+                                                  int(x0 is not None), max_steps, C.byref(st), _dptr(res), C.byref(steps))
+            x = out
+        else:
+            b = np.ascontiguousarray(np.asarray(b, dtype=np.float64)).ravel()
+            if b.shape[0] != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
+            if x0 is None:
+                x = np.zeros(self.N)
+            else:
+                x = np.array(x0, dtype=np.float64).ravel()
+                if x.shape[0] != self.N:
+                    raise CpkError(_lib.CPK_ERR_DIM, "x0 must have n+m entries")
+            rc = lib.cpk_kkt_solve_refined(self.h, _lib.METHODS[name], _dptr(b), M.h, C.byref(make_opts(opts)), _dptr(x),
+                                           int(x0 is not None), max_steps, C.byref(st), _dptr(res), C.byref(steps))
+        # the residuals formed: one per taken driver call, and where a trial was dropped (the loop ended
+        # early without an error) those of the returned x and of that trial
+        dropped = rc == _lib.CPK_OK and steps.value < max_steps
+        rows = res.reshape(max_steps + 1, 4)[:steps.value + (3 if dropped else 1)].copy()
+        if rc != _lib.CPK_OK:
+            try:
+                check(rc)
+            except CpkError as e:
+                e.partial = (x, rows)
+                raise
+        stats, flag = _stats_from(name, st, hist, lq, qr)
+        stats["ptime"], stats["stime"] = st.ptime, st.stime
+        stats["refine_steps"], stats["resid_sums"] = steps.value, rows
+        stats["true_resid0"] = _norms_dict(rows[0], True)  # K.solve's key: with max_steps=0 the stats are K.solve's
+        stats["true_resid"] = self.residual(x, b, out=None, want_r=False)[1]
         return x, stats, flag
 
     def adjoint(self, method, x, gx, M, opts=None, KT=None, lam0=None, out=None):

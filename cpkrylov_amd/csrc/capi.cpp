@@ -1276,6 +1276,71 @@ int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const d
     API_END
 }
 
+// ---- the exactly rounded residual: cpk_kkt_residual's entries with r_i = RN(exact row sum) --------
+// A block is a loop of single-column passes (no panel kernel, no routing): launch_kkt_resid_exact
+// forms a column's r, kkt_sums_kernel takes its sums from the stored r and b in the single-column
+// pass's order, so they are what cpk_kkt_residual's sums would be on that r and b.  r goes to K's
+// work array when the caller wants no R or wants it over Bm (the sums read b after r exists).
+static void kkt_resid_exact_block(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_B, int64_t ldb,
+                                  double *d_R, int64_t ldr, double *d_norms) {
+    const DMat &Kd = K->current();
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    if (!d_R && !d_norms) return;
+    const bool aside = d_norms && (!d_R || d_R == d_B);
+    if (aside && K->Tp.n < (size_t)N) K->Tp.alloc((size_t)N * kMultiKP);  // the panel path's size
+    for (int64_t j = 0; j < k; j++) {
+        const double *b = d_B + j * ldb;
+        double *dst = aside ? K->Tp.p : d_R + j * ldr;
+        launch_kkt_resid_exact(c, Kd, d_Z + j * ldz, b, dst);
+        if (d_norms) launch_kkt_sums(c, Kd, K->n, dst, b, d_norms + 4 * j);
+        if (d_R && aside && N)
+            CPK_HIP(hipMemcpyAsync(d_R + j * ldr, dst, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+    }
+}
+
+int cpk_kkt_residual_exact_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                                  double *d_R, int64_t ldr, double *d_norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
+    if (k == 0) return CPK_OK;
+    kkt_resid_exact_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
+    API_END
+}
+
+int cpk_kkt_residual_exact_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm,
+                                       int64_t ldb, double *d_R, int64_t ldr, double *norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
+    need(norms != nullptr, "NULL argument");
+    if (k == 0) return CPK_OK;
+    Ctx &c = K->ctx->c;
+    DBuf<double> dn;
+    dn.alloc(4 * (size_t)k);
+    kkt_resid_exact_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, dn.p);
+    CPK_HIP(hipMemcpyAsync(norms, dn.p, dn.bytes(), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    API_END
+}
+
+int cpk_kkt_residual_exact(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
+                           int64_t ldr, double *norms) {
+    API_BEGIN
+    check_kkt_resid(K, k, Z, ldz, Bm, ldb, R, ldr);
+    if (k == 0) return CPK_OK;
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    HostBlock dZ(N, k), dB(N, k);
+    DBuf<double> dn;
+    if (norms) dn.alloc(4 * (size_t)k);
+    dZ.up(Z, ldz), dB.up(Bm, ldb);
+    kkt_resid_exact_block(K, k, dZ.d.p, dZ.ld(), dB.d.p, dB.ld(), R ? dB.d.p : nullptr, dB.ld(), dn.p);
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (R) dB.down(R, ldr);
+    if (norms) CPK_HIP(hipMemcpy(norms, dn.p, 4 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+    API_END
+}
+
 // cold: reg_cpkrylov's driver on b (cpk_reg_solve_device's call exactly).  warm: r = b - K*x0, the
 // same driver on r (its shift included, reg_cpkrylov.m:152-175), x = x0 + dx.  res (host, 8):
 // the four sums of the start residual, then those of b - K*x for the returned x.
@@ -1356,6 +1421,116 @@ int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_op
         err = std::current_exception();
     }
     if (N) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (err) std::rethrow_exception(err);
+    API_END
+}
+
+// ---- iterative refinement on the exactly rounded residual (cpk_kkt_solve_refined) ----------------
+// x_0 = x0 (warm) or 0; driver call j = 0 .. max_steps runs reg_solve_device on r_j = the exactly
+// rounded b - K*x_j (cold, j = 0: on b itself, which that residual is) from a zero start and gives
+// the trial x_j + dx_j, one rounding per entry.  r_{j+1} is formed at the trial: unless its sum of
+// squares is below r_j's the trial is dropped and the loop ends with x_j; the last call's trial
+// (j = max_steps) is taken as cpk_kkt_solve takes its own, without a further residual.  A driver
+// error ends the loop with x_j plus whatever the driver wrote.  The driver's vectors, r, dx and the
+// trial live in K (kkt_solve_core's layout plus the trial), at the same addresses on every call.
+static void kkt_refined_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
+                             int max_steps, cpk_stats *stats, double *res, int *steps_out, bool *wrote_x = nullptr) {
+    cpk_mat A = K->A, C = K->C;
+    need(M->ctx == K->ctx, "kkt_solve_refined: M belongs to another context");
+    check_method_dims(A, C, M);
+    Ctx &c = K->ctx->c;
+    Precond &p = *M->p;
+    const int64_t N = K->n + K->m;
+    const DMat &Kd = K->current();
+    const DMat &AC = A->krylov_op(C, p);
+    const ShiftOps so = shift_ops(A, C, p);
+    double *dn = K->norms.p;
+    const size_t wsn = reg_solve_ws(N, K->n), part = reg_solve_ws_part(N), nb = (size_t)N * sizeof(double);
+    if (K->ws.n < wsn + 3 * part) K->ws.alloc(wsn + 3 * part);
+    double *ws = K->ws.p, *r = ws + wsn, *dx = r + part, *xt = dx + part;
+    if (stats) stats->ptime = p.ptime;
+    if (steps_out) *steps_out = 0;
+    if (wrote_x) *wrote_x = true;  // every refusal is behind us: from here on d_x holds an iterate
+    // the four sums of residual `row` (rv against b), to res; returns sum r^2
+    auto sums = [&](const double *rv, int row) {
+        double h[4];
+        launch_kkt_sums(c, Kd, K->n, rv, d_b, dn);
+        CPK_HIP(hipMemcpyAsync(h, dn, sizeof h, hipMemcpyDeviceToHost, c.stream));
+        CPK_HIP(hipStreamSynchronize(c.stream));
+        if (res) std::memcpy(res + 4 * (size_t)row, h, sizeof h);
+        return h[0] + h[1];
+    };
+    auto take_trial = [&] {
+        if (N) CPK_HIP(hipMemcpyAsync(d_x, xt, nb, hipMemcpyDeviceToDevice, c.stream));
+    };
+    double rr;
+    if (!warm) {
+        if (N) CPK_HIP(hipMemsetAsync(d_x, 0, nb, c.stream));
+        rr = sums(d_b, 0);  // the start residual of x = 0 is b
+    } else {
+        launch_kkt_resid_exact(c, Kd, d_x, d_b, r);
+        rr = sums(r, 0);
+    }
+    int applied = 0;
+    for (int j = 0; j <= max_steps; j++) {
+        const bool on_b = !warm && j == 0;
+        double *out = on_b ? xt : dx;
+        CPK_HIP(hipMemsetAsync(out, 0, (size_t)std::max<int64_t>(N, 1) * sizeof(double), c.stream));
+        std::exception_ptr err;
+        try {
+            reg_solve_device(c, method, on_b ? d_b : r, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, out, stats, nullptr, ws);
+        } catch (...) {
+            err = std::current_exception();
+        }
+        if (!on_b) launch_recover(c, N, d_x, dx, xt);
+        if (err || j == max_steps) {
+            take_trial();
+            applied++;
+            CPK_HIP(hipStreamSynchronize(c.stream));
+            if (steps_out) *steps_out = applied - 1;
+            if (err) std::rethrow_exception(err);
+            return;
+        }
+        launch_kkt_resid_exact(c, Kd, xt, d_b, r);
+        const double rn = sums(r, j + 1);
+        if (!(rn < rr)) break;  // no decrease (or a NaN): this dx is not applied
+        take_trial();
+        applied++;
+        rr = rn;
+    }
+    CPK_HIP(hipStreamSynchronize(c.stream));
+    if (steps_out) *steps_out = applied - 1;
+}
+
+int cpk_kkt_solve_refined_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x,
+                                 int warm, int max_steps, cpk_stats *stats, double *res, int *steps_out) {
+    API_BEGIN
+    need(K && M && ((d_b && d_x) || !(K->n + K->m)), "NULL argument");
+    need(max_steps >= 0, "kkt_solve_refined: max_steps >= 0 required");
+    kkt_refined_core(K, method, d_b, M, opts, d_x, warm, max_steps, stats, res, steps_out);
+    API_END
+}
+
+int cpk_kkt_solve_refined(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_opts *opts, double *x, int warm,
+                          int max_steps, cpk_stats *stats, double *res, int *steps_out) {
+    API_BEGIN
+    need(K && M && ((b && x) || !(K->n + K->m)), "NULL argument");
+    need(max_steps >= 0, "kkt_solve_refined: max_steps >= 0 required");
+    Ctx &c = K->ctx->c;
+    const int64_t N = K->n + K->m;
+    DBuf<double> db, dx;
+    h2d(db, b, (size_t)N);
+    if (warm) h2d(dx, x, (size_t)N);
+    else dx.alloc((size_t)std::max<int64_t>(N, 1));
+    std::exception_ptr err;
+    bool wrote_x = false;  // a refusal leaves the caller's x as it is
+    try {
+        kkt_refined_core(K, method, db.p, M, opts, dx.p, warm, max_steps, stats, res, steps_out, &wrote_x);
+    } catch (...) {
+        err = std::current_exception();
+    }
+    if (N && wrote_x) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     CPK_HIP(hipStreamSynchronize(c.stream));
     if (err) std::rethrow_exception(err);
     API_END

@@ -272,6 +272,9 @@ void launch_kkt_sums(Ctx &c, const DMat &K, int64_t n, const double *r, const do
 // K streamed once; every column bit-equal to launch_kkt_resid's r (R == B allowed)
 void launch_kkt_panel(Ctx &c, const DMat &K, int kc, const double *Z, int64_t ldz, const double *B, int64_t ldb, double *R,
                       int64_t ldr);
+// r_i = RN(b_i - sum_e K_ie z_col(e)): the exact sum of b_i and the rows' TwoProd pairs, rounded once
+// to nearest even (a non-finite term: NaN in that row; r == b allowed; independent of the grid)
+void launch_kkt_resid_exact(Ctx &c, const DMat &K, const double *z, const double *b, double *r);
 struct DistCsr;
 void make_dist_dmat(const DistCsr &a, int nranks, DMat &d);
 // allgather the halo of x (local vector) into A.rbuf

@@ -567,7 +567,49 @@ int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_op
                   cpk_stats *stats, double *res);
 int cpk_kkt_solve_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
                          cpk_stats *stats, double *res);
-/* The adjoint of that solve, one right-hand side: with x = K \ b and gx = dL/dx it returns
+/* The exactly rounded true residual: cpk_kkt_residual's three entries with
+ *     r_i = RN( b_i - sum_e K_ie * z_col(e) ),
+ * the EXACT sum of b_i and the TwoProd pairs p = -v*z, q = fma(-v, z, -p) of the row's stored
+ * entries (p + q = -v*z unless the product under- or overflows, the caveat of the exact inner
+ * products), rounded once to nearest even: one definition, whatever the entry order, the grid or
+ * the route a row takes through the kernel; an exact zero is +0.0.  A non-finite term (b_i
+ * included) makes r_i a NaN, in that row only; an empty row gives RN(b_i) = b_i.  The arguments,
+ * the refusals and their order, R == Bm, the NULL outputs and the padding rows are
+ * cpk_kkt_residual's.  norms are the four sums cpk_kkt_residual would return on that r and b
+ * (exact under exact_dots, fixed-order otherwise).  A block is a loop of single-column passes (no
+ * panel kernel, no routing): column j depends neither on k, nor on j, nor on its neighbours. */
+int cpk_kkt_residual_exact(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
+                           int64_t ldr, double *norms);
+int cpk_kkt_residual_exact_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                                  double *d_R, int64_t ldr, double *d_norms);
+int cpk_kkt_residual_exact_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm,
+                                       int64_t ldb, double *d_R, int64_t ldr, double *norms);
+/* Iterative refinement of cpk_kkt_solve on that residual, one right-hand side, all six methods.
+ * x_0 = x0 (warm != 0; x holds it on entry) or 0.  Driver call j = 0 .. max_steps runs the driver
+ * cpk_kkt_solve's warm path runs, from a zero start, on r_j = the exactly rounded b - K*x_j (cold,
+ * j = 0: on b itself, which r_0 then is) and gives the trial x_j + dx_j, one rounding per entry.
+ * EACH DRIVER CALL'S STOP TEST RUNS ON ITS CORRECTION SYSTEM: atol and rtol are relative to the
+ * initial preconditioned residual of r_j, not of b.  For j < max_steps the next residual r_{j+1}
+ * is formed at the trial: if its sum of squares is not below r_j's (a NaN included) the trial is
+ * dropped, x = x_j is returned and the loop ends; otherwise x_{j+1} is the trial.  The trial of
+ * call j = max_steps is taken without a further residual, so max_steps == 0, cold, is
+ * cpk_kkt_solve's cold solve.  steps_out (may be NULL): the corrections in the returned x, that is
+ * the driver calls after the first whose trial was taken; -1 when the first call's own trial was
+ * dropped and x is x_0.  res (HOST memory in both variants,
+ * 4 (max_steps + 1) doubles, may be NULL): row j the four sums (cpk_kkt_residual's order) of r_j
+ * for every residual formed, a dropped trial's included: steps_out + 1 rows when the loop ran to
+ * its end or stopped inside the driver, steps_out + 3 when a trial was dropped (steps_out <
+ * max_steps with CPK_OK: the last two rows are those of the returned x and of the dropped trial);
+ * rows beyond are not written.  stats: the last driver call's.  A stop inside the driver
+ * (CPK_ERR_INDEFINITE) ends the loop and is returned with the driver's own code; x is then x_j plus
+ * whatever the driver wrote.  Refusals are cpk_kkt_solve's (an Operator has no K; a distributed
+ * context has none either), and CPK_ERR_ARGS for max_steps < 0; a refusal writes nothing: the host
+ * entry leaves x as it was. */
+int cpk_kkt_solve_refined(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_opts *opts, double *x, int warm,
+                          int max_steps, cpk_stats *stats, double *res, int *steps_out);
+int cpk_kkt_solve_refined_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x,
+                                 int warm, int max_steps, cpk_stats *stats, double *res, int *steps_out);
+/* The adjoint of cpk_kkt_solve, one right-hand side: with x = K \ b and gx = dL/dx it returns
  * lam = K' \ gx = dL/db and the gradients with respect to the values of K's own handles, each in
  * its handle's creating call's value order (cpk_mat_sample_outer on that handle; x = [xx; xy],
  * lam = [lx; ly]):
