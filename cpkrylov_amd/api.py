@@ -1096,6 +1096,22 @@ def _norms_dict(nr, vector):
     return {k: float(v[0]) for k, v in d.items()} if vector else d
 
 
+def _raise_partial(rc, partial):
+    """The C status rc, unless it is CPK_OK, as its CpkError (`check`) carrying `partial`"""
+    try:
+        check(rc)
+    except CpkError as e:
+        e.partial = partial
+        raise
+
+
+def _verified_stats(stats, st, sums0, sums):
+    """What K's solves add to a column's stats: the times, and the sums and norms of the start
+    residual and of the returned x's (four sums each, as the C entries return them)"""
+    stats["ptime"], stats["stime"] = st.ptime, st.stime
+    stats["true_resid0"], stats["true_resid"] = _norms_dict(sums0, True), _norms_dict(sums, True)
+
+
 class KKT:
     """The saddle-point operator K = [A B'; B -C] of the system reg_cpkrylov solves (A, B, C as
     the solvers take them: C is the positive block; A may be nonsymmetric), resident on the GPU.
@@ -1233,49 +1249,17 @@ class KKT:
         warm start passes x0=out, which holds x0 on entry and is updated in place.  A stop inside
         the driver raises its own error, carrying `partial` = (x0 plus whatever the driver wrote,
         the eight sums)."""
-        name = getattr(method, "_cpk_method", method)
-        if name not in _lib.METHODS:
-            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
-        if any(isinstance(v, Operator) for v in (b, M, x0, out)):
-            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.solve is matrix-only: K's (1,1) block is the matrix it was built on")
-        if not isinstance(M, opLDL2):
-            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        name = self._solving_method(method, M, (b, x0, out),
+                                    "K.solve is matrix-only: K's (1,1) block is the matrix it was built on")
+        (bp, xp), x, _ = self._one_rhs("solve", (b,), x0, out, ("b", "x0", "out"))
         st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
         res = np.zeros(8)
-        if _is_device(b):
-            if out is None or not _is_device(out):
-                raise CpkError(_lib.CPK_ERR_ARGS, "solve on device operands: pass the result tensor as out=")
-            if x0 is not None and x0 is not out:
-                raise CpkError(_lib.CPK_ERR_ARGS, "solve on device operands: x0 is out itself (x0 is updated in place)")
-            bp, kb, _ = _device_operand(b, "b", self.N)
-            xp, kx, _ = _device_operand(out, "out", self.N)
-            if kb != 1 or kx != 1:
-                raise CpkError(_lib.CPK_ERR_DIM, "solve takes one right-hand side of N entries")
-            rc = lib.cpk_kkt_solve_device(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp,
-                                          int(x0 is not None), C.byref(st), _dptr(res))
-            x = out
-        else:
-            b = np.ascontiguousarray(np.asarray(b, dtype=np.float64)).ravel()
-            if b.shape[0] != self.N:
-                raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
-            if x0 is None:
-                x = np.zeros(self.N)
-            else:
-                x = np.array(x0, dtype=np.float64).ravel()
-                if x.shape[0] != self.N:
-                    raise CpkError(_lib.CPK_ERR_DIM, "x0 must have n+m entries")
-            rc = lib.cpk_kkt_solve(self.h, _lib.METHODS[name], _dptr(b), M.h, C.byref(make_opts(opts)), _dptr(x),
-                                   int(x0 is not None), C.byref(st), _dptr(res))
-        if rc != _lib.CPK_OK:
-            try:
-                check(rc)
-            except CpkError as e:
-                e.partial = (x, res.copy())  # x0 plus whatever the driver wrote, and the sums
-                raise
+        entry = lib.cpk_kkt_solve_device if _is_device(x) else lib.cpk_kkt_solve
+        rc = entry(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp, int(x0 is not None), C.byref(st),
+                   _dptr(res))
+        _raise_partial(rc, (x, res))  # x0 plus whatever the driver wrote, and the sums
         stats, flag = _stats_from(name, st, hist, lq, qr)
-        stats["ptime"], stats["stime"] = st.ptime, st.stime
-        stats["true_resid0"] = _norms_dict(res[:4], True)
-        stats["true_resid"] = _norms_dict(res[4:], True)
+        _verified_stats(stats, st, res[:4], res[4:])
         return x, stats, flag
 
     def solve_refined(self, method, b, M, opts=None, x0=None, max_steps=3, out=None):
@@ -1294,57 +1278,27 @@ class KKT:
         `solve` sets it (the plain residual of the returned x).  Operands and out= are `solve`'s; a
         stop inside the driver raises its error with `partial` = (x_j plus whatever the driver wrote,
         resid_sums)."""
-        name = getattr(method, "_cpk_method", method)
-        if name not in _lib.METHODS:
-            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
-        if any(isinstance(v, Operator) for v in (b, M, x0, out)):
-            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.solve_refined is matrix-only: K's (1,1) block is the matrix it was built on")
-        if not isinstance(M, opLDL2):
-            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        name = self._solving_method(method, M, (b, x0, out),
+                                    "K.solve_refined is matrix-only: K's (1,1) block is the matrix it was built on")
         max_steps = int(max_steps)
         if max_steps < 0:
             raise CpkError(_lib.CPK_ERR_ARGS, "max_steps >= 0 required")
+        (bp, xp), x, (b,) = self._one_rhs("solve_refined", (b,), x0, out, ("b", "x0", "out"))
         st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
         res, steps = np.zeros(4 * (max_steps + 1)), C.c_int(0)
-        if _is_device(b):
-            if out is None or not _is_device(out):
-                raise CpkError(_lib.CPK_ERR_ARGS, "solve_refined on device operands: pass the result tensor as out=")
-            if x0 is not None and x0 is not out:
-                raise CpkError(_lib.CPK_ERR_ARGS, "solve_refined on device operands: x0 is out itself (x0 is updated in place)")
-            bp, kb, _ = _device_operand(b, "b", self.N)
-            xp, kx, _ = _device_operand(out, "out", self.N)
-            if kb != 1 or kx != 1:
-                raise CpkError(_lib.CPK_ERR_DIM, "solve_refined takes one right-hand side of N entries")
-            rc = lib.cpk_kkt_solve_refined_device(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp,
-                                                  int(x0 is not None), max_steps, C.byref(st), _dptr(res), C.byref(steps))
-            x = out
-        else:
-            b = np.ascontiguousarray(np.asarray(b, dtype=np.float64)).ravel()
-            if b.shape[0] != self.N:
-                raise CpkError(_lib.CPK_ERR_DIM, "b must have n+m entries")
-            if x0 is None:
-                x = np.zeros(self.N)
-            else:
-                x = np.array(x0, dtype=np.float64).ravel()
-                if x.shape[0] != self.N:
-                    raise CpkError(_lib.CPK_ERR_DIM, "x0 must have n+m entries")
-            rc = lib.cpk_kkt_solve_refined(self.h, _lib.METHODS[name], _dptr(b), M.h, C.byref(make_opts(opts)), _dptr(x),
-                                           int(x0 is not None), max_steps, C.byref(st), _dptr(res), C.byref(steps))
+        entry = lib.cpk_kkt_solve_refined_device if _is_device(x) else lib.cpk_kkt_solve_refined
+        rc = entry(self.h, _lib.METHODS[name], bp, M.h, C.byref(make_opts(opts)), xp, int(x0 is not None), max_steps,
+                   C.byref(st), _dptr(res), C.byref(steps))
         # the residuals formed: one per taken driver call, and where a trial was dropped (the loop ended
         # early without an error) those of the returned x and of that trial
         dropped = rc == _lib.CPK_OK and steps.value < max_steps
         rows = res.reshape(max_steps + 1, 4)[:steps.value + (3 if dropped else 1)].copy()
-        if rc != _lib.CPK_OK:
-            try:
-                check(rc)
-            except CpkError as e:
-                e.partial = (x, rows)
-                raise
+        _raise_partial(rc, (x, rows))
         stats, flag = _stats_from(name, st, hist, lq, qr)
-        stats["ptime"], stats["stime"] = st.ptime, st.stime
         stats["refine_steps"], stats["resid_sums"] = steps.value, rows
-        stats["true_resid0"] = _norms_dict(rows[0], True)  # K.solve's key: with max_steps=0 the stats are K.solve's
-        stats["true_resid"] = self.residual(x, b, out=None, want_r=False)[1]
+        # true_resid0 is K.solve's key: with max_steps=0 the stats are K.solve's
+        _verified_stats(stats, st, rows[0], rows[0])
+        stats["true_resid"] = self.residual(x, b, out=None, want_r=False)[1]  # the plain residual of the returned x
         return x, stats, flag
 
     def adjoint(self, method, x, gx, M, opts=None, KT=None, lam0=None, out=None):
@@ -1364,76 +1318,25 @@ class KKT:
         and "dA", "dB", "dC" each optional -- a gradient that is absent is not formed.  A stop
         inside the driver raises its own error, carrying `partial` = (lambda as far as the driver
         wrote it, the eight sums); the gradient arrays are then untouched."""
-        name = getattr(method, "_cpk_method", method)
-        if name not in _lib.METHODS:
-            raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
-        if any(isinstance(v, Operator) for v in (x, gx, M, KT, lam0)):
-            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K.adjoint is matrix-only: an Operator has no entries to take a gradient on")
-        if not isinstance(M, opLDL2):
-            raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
+        name = self._solving_method(method, M, (x, gx, KT, lam0),
+                                    "K.adjoint is matrix-only: an Operator has no entries to take a gradient on")
         if KT is not None and not isinstance(KT, KKT):
             raise CpkError(_lib.CPK_ERR_ARGS, "KT must be a KKT operator (of A.T, B, C)")
         out = dict(out or {})
         if set(out) - {"db", "dA", "dB", "dC"}:
             raise CpkError(_lib.CPK_ERR_ARGS, "adjoint: out= holds db, dA, dB, dC")
+        (xp, gxp, lp), lam, _ = self._one_rhs("adjoint", (x, gx), lam0, out.get("db"), ("x", "gx", "lam0", "out['db']"),
+                                              fill_host_out=True)
+        device = _is_device(lam)
+        gp = self._grad_args(out, device)
         st, hist, lq, qr = _new_stats(_hist_cap(name, opts, self.n, self.m))
         res = np.zeros(8)
-        counts = [h.info()["entries"] for h in (self.A, self.B, self.C)]
-        kth = KT.h if KT is not None else None
-        if _is_device(x) or _is_device(gx):
-            if not (_is_device(x) and _is_device(gx) and _is_device(out.get("db"))):
-                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint on device operands: x, gx and out['db'] are device tensors")
-            if lam0 is not None and lam0 is not out["db"]:
-                raise CpkError(_lib.CPK_ERR_ARGS, "adjoint on device operands: lam0 is out['db'] itself (updated in place)")
-            ptrs = []
-            for v, what in ((x, "x"), (gx, "gx"), (out["db"], "out['db']")):
-                p, k, _ = _device_operand(v, what, self.N)
-                if k != 1:
-                    raise CpkError(_lib.CPK_ERR_DIM, "adjoint takes one right-hand side of N entries")
-                ptrs.append(p)
-            gp = []
-            for key, cnt in zip(("dA", "dB", "dC"), counts):
-                g = out.get(key)
-                if g is None:
-                    gp += [C.c_void_p(None), 0]
-                    continue
-                if not _is_device(g):
-                    raise CpkError(_lib.CPK_ERR_ARGS, f"adjoint on device operands: out[{key!r}] is a device tensor")
-                gp += [_device_operand(g, key, cnt)[0], int(g.numel())]
-            rc = lib.cpk_kkt_adjoint_device(self.h, kth, _lib.METHODS[name], ptrs[0], ptrs[1], M.h, C.byref(make_opts(opts)),
-                                            ptrs[2], int(lam0 is not None), *gp, C.byref(st), _dptr(res))
-            lam = out["db"]
-        else:
-            x, gx = (np.ascontiguousarray(np.asarray(v, dtype=np.float64)).ravel() for v in (x, gx))
-            if x.shape[0] != self.N or gx.shape[0] != self.N:
-                raise CpkError(_lib.CPK_ERR_DIM, "x and gx must have n+m entries")
-            for key, cnt in zip(("db", "dA", "dB", "dC"), [self.N] + counts):
-                g = out.setdefault(key, np.zeros(cnt))
-                if not (isinstance(g, np.ndarray) and g.dtype == np.float64 and g.flags.c_contiguous):
-                    raise CpkError(_lib.CPK_ERR_ARGS, f"adjoint: out[{key!r}] is a contiguous float64 array")
-            lam = out["db"]
-            if lam.size != self.N:
-                raise CpkError(_lib.CPK_ERR_DIM, "out['db'] must have n+m entries")
-            if lam0 is not None:
-                l0 = np.asarray(lam0, dtype=np.float64).ravel()
-                if l0.shape[0] != self.N:
-                    raise CpkError(_lib.CPK_ERR_DIM, "lam0 must have n+m entries")
-                lam[:] = l0
-            gp = []
-            for key in ("dA", "dB", "dC"):
-                gp += [_dptr(out[key]) if out[key].size else None, out[key].size]
-            rc = lib.cpk_kkt_adjoint(self.h, kth, _lib.METHODS[name], _dptr(x), _dptr(gx), M.h, C.byref(make_opts(opts)),
-                                     _dptr(lam), int(lam0 is not None), *gp, C.byref(st), _dptr(res))
-        if rc != _lib.CPK_OK:
-            try:
-                check(rc)
-            except CpkError as e:
-                e.partial = (lam, res.copy())
-                raise
+        entry = lib.cpk_kkt_adjoint_device if device else lib.cpk_kkt_adjoint
+        rc = entry(self.h, KT.h if KT is not None else None, _lib.METHODS[name], xp, gxp, M.h, C.byref(make_opts(opts)), lp,
+                   int(lam0 is not None), *gp, C.byref(st), _dptr(res))
+        _raise_partial(rc, (lam, res))
         stats, flag = _stats_from(name, st, hist, lq, qr)
-        stats["ptime"], stats["stime"] = st.ptime, st.stime
-        stats["true_resid0"] = _norms_dict(res[:4], True)
-        stats["true_resid"] = _norms_dict(res[4:], True)
+        _verified_stats(stats, st, res[:4], res[4:])
         return dict(db=lam, dA=out.get("dA"), dB=out.get("dB"), dC=out.get("dC"), stats=stats, flag=flag)
 
     # ---- the block forms: N x k blocks (a (k, N) row-major device tensor is the N x k block) ----------
@@ -1460,21 +1363,60 @@ class KKT:
             ptrs.append(p)
         return ptrs, k, max(self.N, 1)
 
-    def _block_method(self, method, M, *operands):
+    _BLOCK_MATRIX_ONLY = "K's block entries are matrix-only: K's (1,1) block is the matrix it was built on"
+
+    def _solving_method(self, method, M, operands, matrix_only):
+        """The method's name after the checks the five solving methods share, in their order: a known
+        method, no Operator among M and the operands (matrix_only: the caller's refusal), M an opLDL2"""
         name = getattr(method, "_cpk_method", method)
         if name not in _lib.METHODS:
             raise CpkError(_lib.CPK_ERR_ARGS, f"unknown method {method!r}")
-        if any(isinstance(v, Operator) for v in (M,) + operands):
-            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, "K's block entries are matrix-only: K's (1,1) block is the matrix it was built on")
+        if any(isinstance(v, Operator) for v in (M,) + tuple(operands)):
+            raise CpkError(_lib.CPK_ERR_UNSUPPORTED, matrix_only)
         if not isinstance(M, opLDL2):
             raise CpkError(_lib.CPK_ERR_ARGS, "M must be an opLDL2 operator")
         return name
 
+    def _one_rhs(self, who, inputs, x0, out, names, fill_host_out=False):
+        """One right-hand side for the single-column C entries.  inputs: the vectors the entry reads
+        (the right-hand side last); x0: the start, or None; names: the inputs', x0's and out's.
+        Device form (an input is a device tensor): the inputs and out are device tensors of one column
+        of N values, and x0 is out itself.  Host form: the inputs ravelled, N entries each; the result
+        is a new array -- or out, filled in place, where fill_host_out -- with x0 copied into it.
+        Returns ([the inputs' pointers..., the result's], the result, the inputs as marshalled)."""
+        *in_names, x0_name, out_name = names
+        if any(_is_device(v) for v in inputs):
+            if not (all(_is_device(v) for v in inputs) and _is_device(out)):
+                raise CpkError(_lib.CPK_ERR_ARGS,
+                               f"{who} on device operands: {', '.join(in_names)} and {out_name} are device tensors")
+            if x0 is not None and x0 is not out:
+                raise CpkError(_lib.CPK_ERR_ARGS, f"{who} on device operands: {x0_name} is {out_name} itself (updated in place)")
+            ptrs = []
+            for v, what in zip(tuple(inputs) + (out,), in_names + [out_name]):
+                p, k, _ = _device_operand(v, what, self.N)
+                if k != 1:
+                    raise CpkError(_lib.CPK_ERR_DIM, f"{who} takes one right-hand side of N entries")
+                ptrs.append(p)
+            return ptrs, out, tuple(inputs)
+        vals = tuple(np.ascontiguousarray(np.asarray(v, dtype=np.float64)).ravel() for v in inputs)
+        for v, what in zip(vals, in_names):
+            if v.shape[0] != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, f"{what} must have n+m entries")
+        x = out if fill_host_out and out is not None else np.zeros(self.N)
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+            raise CpkError(_lib.CPK_ERR_ARGS, f"{who}: {out_name} is a contiguous float64 array")
+        if x.size != self.N:
+            raise CpkError(_lib.CPK_ERR_DIM, f"{out_name} must have n+m entries")
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64).ravel()
+            if x0.shape[0] != self.N:
+                raise CpkError(_lib.CPK_ERR_DIM, f"{x0_name} must have n+m entries")
+            x[:] = x0
+        return [_dptr(v) for v in vals] + [_dptr(x)], x, vals
+
     def _block_stats(self, sts, stats, res, k):
         for j in range(k):
-            stats[j]["ptime"], stats[j]["stime"] = sts[j].ptime, sts[j].stime
-            stats[j]["true_resid0"] = _norms_dict(res[8 * j:8 * j + 4], True)
-            stats[j]["true_resid"] = _norms_dict(res[8 * j + 4:8 * j + 8], True)
+            _verified_stats(stats[j], sts[j], res[8 * j:8 * j + 4], res[8 * j + 4:8 * j + 8])
 
     def solve_block(self, method, B, M, opts=None, X0=None, out=None):
         """X, stats, flags = K.solve_block(method, B, M, opts, X0): `solve` for the k columns of an
@@ -1485,7 +1427,7 @@ class KKT:
         Device operands as `residual` takes blocks: B a (k, N) device tensor, the result in out=,
         and a warm start passes X0=out.  A column whose driver stops raises its error carrying
         `columns` (the per-column status codes) and `partial` = (X, stats, flags)."""
-        name = self._block_method(method, M, B, X0, out)
+        name = self._solving_method(method, M, (B, X0, out), self._BLOCK_MATRIX_ONLY)
         if _is_device(B):
             if out is None or not _is_device(out):
                 raise CpkError(_lib.CPK_ERR_ARGS, "solve_block on device operands: pass the result tensor as out=")
@@ -1585,7 +1527,7 @@ class KKT:
         takes them: on device, out["db"] is required and Lam0 is out["db"] itself.  A column whose
         driver stops raises its error (`columns`, `partial` = (Lam, stats, flags)); the gradient
         arrays are then untouched."""
-        name = self._block_method(method, M, X, GX, Lam0)
+        name = self._solving_method(method, M, (X, GX, Lam0), self._BLOCK_MATRIX_ONLY)
         out = dict(out or {})
         if set(out) - {"db", "dA", "dB", "dC"}:
             raise CpkError(_lib.CPK_ERR_ARGS, "adjoint_block: out= holds db, dA, dB, dC")

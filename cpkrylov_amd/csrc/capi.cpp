@@ -1,5 +1,5 @@
-// capi.cpp -- the extern "C" boundary of libcpk (include/cpk.h).  Every entry point converts
-// C++ exceptions into a cpk_status code plus a thread-local message.
+// capi.cpp -- the extern "C" boundary of libcpk (include/cpk.h).  Every entry point checks, stages host
+// arrays and converts C++ exceptions into a cpk_status code plus a thread-local message.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -8,221 +8,12 @@
 #include <cmath>
 #include <cstring>
 #include <exception>
-#include <map>
-#include <memory>
 #include <new>
 #include <string>
 
-#include "cpk.h"
-#include "dev.hpp"
-#include "dist.hpp"
-#include "solvers.hpp"
-
-using namespace cpk;
-
-struct cpk_ctx_s {
-    Ctx c;
-    std::unique_ptr<Comm> comm;
-};
-
-struct cpk_simgroup_s {
-    SimGroup *g = nullptr;
-    ~cpk_simgroup_s() {
-        if (g) simgroup_destroy(g);
-    }
-};
-
-// blkdiag(A, C) on the device with the values generations of A and C it holds
-struct KrylovOp {
-    std::unique_ptr<DMat> m;
-    uint64_t va = 0, vc = 0;
-};
-
-struct cpk_mat_s {
-    cpk_ctx_s *ctx = nullptr;
-    uint64_t gen = 0;   // names the handle and its sparsity: never changes
-    uint64_t vgen = 0;  // values generation: +1 per successful cpk_mat_set_values[_device]
-    HCsr h;             // h.val may lag the device copy (h_stale): read the values through host()
-    ValueMap vm;        // stored entry <- entries of the creating call's value array
-    DValueMap dvm;      // its device copy, uploaded by the first update from device memory
-    bool h_stale = false;
-    bool hashed = false;
-    uint64_t phash = 0;
-    std::unique_ptr<DMat> d;                // lazily uploaded
-    std::map<uint64_t, KrylovOp> ac;        // blkdiag(this, C) keyed by C's generation
-    // the host copy with current values: downloaded after an update from device memory
-    const HCsr &host() {
-        if (h_stale) {
-            Ctx &c = ctx->c;
-            if (d->nnz) CPK_HIP(hipMemcpyAsync(h.val.data(), d->val.p, (size_t)d->nnz * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-            CPK_HIP(hipStreamSynchronize(c.stream));
-            h_stale = false;
-        }
-        return h;
-    }
-    uint64_t pattern_hash() {
-        if (!hashed) phash = pattern_hash_one(h), hashed = true;
-        return phash;
-    }
-    const DMat &dev() {
-        if (!ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
-        if (!d) {
-            d = std::make_unique<DMat>();
-            make_dmat(h, *d);  // no device copy yet: h is current
-        }
-        return *d;
-    }
-    // distributed rows follow the preconditioner's dof map, so they are
-    // cached in the Precond itself (Precond::dist_ops), keyed by the matrices' generations: they
-    // die with the preconditioner, and a new preconditioner never sees an old one's rows
-    const DMat &krylov_op(cpk_mat_s *C, Precond &M) {
-        if (M.dist != ctx->c.dist())
-            throw Error(CPK_ERR_ARGS, "engine option dist1 changed after the preconditioner was built");
-        if (!M.dist) return blkdiag_with(C);
-        auto &slot = M.dist_ops[{'K', gen, C->gen}];
-        if (!slot) {
-            auto m = std::make_unique<DMat>();
-            make_dist_dmat(dist_csr(blkdiag(host(), C->host()), *M.dofmap, ctx->c.rank, false, kKrylovSpare), ctx->c.nranks,
-                           *m);
-            slot = std::move(m);
-        }
-        return *slot;
-    }
-    // shift rows of a distributed preconditioner: A*xy0(1:n) and B'*xy0(n+1:N), x-part rows
-    std::pair<const DMat *, const DMat *> shift_ops(Precond &M) {
-        auto &sa = M.dist_ops[{'A', gen, 0}];
-        auto &sb = M.dist_ops[{'B', gen, 0}];
-        if (!sa || !sb) {
-            const int64_t n = M.gn, N = M.gN;
-            HCsr a = host(), bt;
-            a.ncols = N;
-            bt.nrows = n, bt.ncols = N;
-            bt.ptr.assign(n + 1, 0);
-            for (int64_t i = 0; i < n; i++) {
-                for (int64_t q = M.Kp.ptr[i]; q < M.Kp.ptr[i + 1]; q++)
-                    if (M.Kp.ind[q] >= n) bt.ind.push_back(M.Kp.ind[q]), bt.val.push_back(M.Kp.val[q]);
-                bt.ptr[i + 1] = (int64_t)bt.ind.size();
-            }
-            auto ma = std::make_unique<DMat>(), mb = std::make_unique<DMat>();
-            make_dist_dmat(dist_csr(a, *M.dofmap, ctx->c.rank, true), ctx->c.nranks, *ma);
-            make_dist_dmat(dist_csr(bt, *M.dofmap, ctx->c.rank, true), ctx->c.nranks, *mb);
-            sa = std::move(ma), sb = std::move(mb);
-        }
-        return {sa.get(), sb.get()};
-    }
-    // this handle's n rows come first in blkdiag (hostsparse.cpp), C's after them, so the
-    // operator's value array is [A's values; C's values]: a refresh is one copy per stale half
-    void refresh_half(Ctx &c, cpk_mat_s *src, double *dst) {
-        const size_t bytes = (size_t)src->h.nnz() * sizeof(double);
-        if (!bytes) return;
-        if (src->d) {
-            CPK_HIP(hipMemcpyAsync(dst, src->d->val.p, bytes, hipMemcpyDeviceToDevice, c.stream));
-        } else {  // never uploaded, so its host copy is current
-            CPK_HIP(hipMemcpyAsync(dst, src->h.val.data(), bytes, hipMemcpyHostToDevice, c.stream));
-            CPK_HIP(hipStreamSynchronize(c.stream));
-        }
-    }
-    const DMat &blkdiag_with(cpk_mat_s *C) {
-        if (!ctx) throw Error(CPK_ERR_ARGS, "host-only matrix (created with ctx == NULL) used on the device");
-        auto it = ac.find(C->gen);
-        if (it == ac.end()) {
-            KrylovOp op;
-            op.va = vgen, op.vc = C->vgen;
-            op.m = std::make_unique<DMat>();
-            make_dmat(blkdiag(host(), C->host()), *op.m);
-            it = ac.emplace(C->gen, std::move(op)).first;
-        }
-        KrylovOp &op = it->second;
-        if (op.va != vgen || op.vc != C->vgen) {
-            // lazily, at the next use after an update of either matrix; the value array keeps
-            // its address, so graphs captured on the operator replay on the new values
-            DMat &m = *op.m;
-            if (m.nnz != h.nnz() + C->h.nnz() || m.nrows != h.nrows + C->h.nrows || (int64_t)m.val.n != m.nnz)
-                throw Error(CPK_ERR_ARGS, "blkdiag(A, C): the cached operator is not [A's entries; C's entries]");
-            if (op.va != vgen) refresh_half(ctx->c, this, m.val.p), op.va = vgen;
-            if (op.vc != C->vgen) refresh_half(ctx->c, C, m.val.p + h.nnz()), op.vc = C->vgen;
-        }
-        return *op.m;
-    }
-};
-
-// The operator-valued A: the caller's callback, and blkdiag(0, C) -- n empty rows, then C's rows
-// with their columns moved past n -- keyed by C's generation as cpk_mat_s::ac is.  Its value
-// array is C's values, so an update of C is one copy at the next use, to the same address.
-struct cpk_op_s {
-    cpk_ctx_s *ctx = nullptr;
-    int64_t n = 0;
-    cpk_op_fn fn = nullptr;
-    void *user = nullptr;
-    int flags = 0;
-    uint64_t gen = 0;
-    int64_t calls = 0, fails = 0;
-    std::map<uint64_t, KrylovOp> zc;
-    OpHook hook() { return OpHook{fn, user, gen, flags, &calls, &fails, nullptr, nullptr}; }
-    const DMat &krylov_op(cpk_mat_s *C) {
-        auto it = zc.find(C->gen);
-        if (it == zc.end()) {
-            HCsr Z;
-            Z.nrows = Z.ncols = n;
-            Z.ptr.assign((size_t)n + 1, 0);
-            KrylovOp op;
-            op.vc = C->vgen;
-            op.m = std::make_unique<DMat>();
-            make_dmat(blkdiag(Z, C->host()), *op.m);
-            it = zc.emplace(C->gen, std::move(op)).first;
-        }
-        KrylovOp &op = it->second;
-        if (op.vc != C->vgen) {
-            DMat &m = *op.m;
-            if (m.nnz != C->h.nnz() || m.nrows != n + C->h.nrows || (int64_t)m.val.n != m.nnz)
-                throw Error(CPK_ERR_ARGS, "blkdiag(0, C): the cached operator does not hold C's entries");
-            C->refresh_half(ctx->c, C, m.val.p), op.vc = C->vgen;
-        }
-        return *op.m;
-    }
-};
-
-// K = [A B'; B -C] on the device in assemble_kp's entry order, with the handles' generations it
-// holds and the map from their stored values (kp_value_sources' order) to its value array
-struct cpk_kkt_s {
-    cpk_ctx_s *ctx = nullptr;
-    cpk_mat_s *A = nullptr, *B = nullptr, *C = nullptr;  // must outlive K
-    uint64_t gen[3] = {0, 0, 0}, vgen[3] = {0, 0, 0};
-    int64_t n = 0, m = 0, refreshes = 0;
-    DMat K;
-    DBuf<uint32_t> src;  // entry q <- entry src[q] of [A's values; B's values; C's values]
-    DBuf<double> norms;  // the device side of a call's sums (8: cpk_kkt_solve's res)
-    // the block residual's routing (0: by kKktPanelMinCols, 1: always the panel, 2: always the loop),
-    // the panels run so far, and the panel path's work array (N * kMultiKP), allocated on first use
-    int route = 0;
-    int64_t panels = 0;
-    DBuf<double> Tp;
-    DBuf<double> ws;  // cpk_kkt_solve's vectors (kkt_solve_core), allocated by the first solve and kept
-    // the block forms (cpk_kkt_solve_multi, cpk_kkt_sample_multi), each grown on first use and kept:
-    // the warm start's residual and correction blocks (2 N k), the device side of the sums (12 k) and
-    // the sampler's operands: the interleaved panels of X and Lam (2 * panel_count(k) * 8 N) or, on the
-    // other route, gB's staged 2 k columns (2 k N)
-    DBuf<double> wsb, normsb, panel_ops;
-    // the block sampler's routing (0: by sample_panel_rule, 1: always the panel kernel, 2: always the
-    // run-time-k kernel) and the calls that took the panel kernel so far
-    int sample_route = 0;
-    int64_t sample_panels = 0;
-    // the operator on the handles' current values: a device gather where a values generation
-    // moved (the value array keeps its address; nothing goes through the host)
-    const DMat &current() {
-        if (A->gen != gen[0] || B->gen != gen[1] || C->gen != gen[2])
-            throw Error(CPK_ERR_ARGS, "kkt: a matrix handle of K was destroyed or replaced");
-        if (A->vgen != vgen[0] || B->vgen != vgen[1] || C->vgen != vgen[2]) {
-            const DMat &a = A->dev(), &b = B->dev(), &c = C->dev();
-            if (a.nnz + 2 * b.nnz + c.nnz != K.nnz || (int64_t)src.n != K.nnz)
-                throw Error(CPK_ERR_ARGS, "kkt: the value map does not match the handles");
-            launch_kkt_gather(ctx->c, src.p, K.nnz, a.val.p, a.nnz, b.val.p, b.nnz, c.val.p, K.val.p);
-            vgen[0] = A->vgen, vgen[1] = B->vgen, vgen[2] = C->vgen;
-            refreshes++;
-        }
-        return K;
-    }
-};
+#include "handles.hpp"
+#include "kkt_driver.hpp"
+#include "staging.hpp"
 
 struct cpk_analysis_s {
     Analysis an;
@@ -238,11 +29,6 @@ struct cpk_plan_s {
     RankPlan rp;
     DistCsr kp, ac, ab;
     int64_t n = 0, m = 0;
-};
-
-struct cpk_pc_s {
-    cpk_ctx_s *ctx = nullptr;
-    std::unique_ptr<Precond> p;
 };
 
 static thread_local std::string g_err;
@@ -264,16 +50,6 @@ static std::atomic<uint64_t> g_gen{1};
         return CPK_ERR_ARGS;                                     \
     }                                                            \
     return CPK_OK;
-
-static void need(bool cond, const char *msg) {
-    if (!cond) throw Error(CPK_ERR_ARGS, msg);
-}
-
-template <class T>
-static void h2d(DBuf<T> &d, const T *h, size_t n) {
-    d.alloc(n);
-    if (n) CPK_HIP(hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice));
-}
 
 // ---- distributed host vectors: global on every rank <-> local slices on the device ----------
 static void scatter_global(const Precond &p, const double *h_glob, int64_t len_local, DBuf<double> &d) {
@@ -299,7 +75,6 @@ static void gather_global(Ctx &c, const Precond &p, const double *d_loc, double 
     for (int64_t g = 0; g < dm.N; g++) h_glob[g] = h[(size_t)dm.owner[g] * mx + dm.lidx[g]];
 }
 
-// ---- host arrays of the host-array entries <-> device memory --------------------------------------
 // a host vector of the preconditioner's layout: the rank's slice (or the whole) up, all of it down
 static void stage_up(const Precond &p, const double *h, int64_t len, DBuf<double> &d) {
     if (p.dist) scatter_global(p, h, len, d);
@@ -313,24 +88,6 @@ static void stage_down(Ctx &c, const Precond &p, const double *d, double *h) {
         CPK_HIP(hipStreamSynchronize(c.stream));
     }
 }
-// rows x k of a host block with leading dimension ld, packed on the device (leading dimension
-// ld(): rows, at least 1); the caller's padding rows are never touched
-struct HostBlock {
-    DBuf<double> d;
-    int64_t rows, k;
-    HostBlock(int64_t rows_, int64_t k_) : rows(rows_), k(k_) { d.alloc((size_t)ld() * (size_t)k); }
-    int64_t ld() const { return std::max<int64_t>(rows, 1); }
-    void up(const double *H, int64_t ldh) {
-        if (rows) CPK_HIP(hipMemcpy2D(d.p, ld() * sizeof(double), H, (size_t)ldh * sizeof(double), rows * sizeof(double),
-                                      (size_t)k, hipMemcpyHostToDevice));
-    }
-    // rows [row0, row0 + nrows) of every column (default: all rows)
-    void down(double *H, int64_t ldh, int64_t row0 = 0, int64_t nrows = -1) const {
-        if (nrows < 0) nrows = rows;
-        if (nrows) CPK_HIP(hipMemcpy2D(H, (size_t)ldh * sizeof(double), d.p + row0, ld() * sizeof(double),
-                                       nrows * sizeof(double), (size_t)k, hipMemcpyDeviceToHost));
-    }
-};
 
 extern "C" {
 
@@ -917,12 +674,6 @@ int cpk_pc_pivot_shift(cpk_pc M, double *E) {
     API_END
 }
 
-static void check_method_dims(cpk_mat A, cpk_mat C, const cpk_pc_s *M) {
-    need(A && C && M, "NULL argument");
-    if (A->h.nrows != A->h.ncols || C->h.nrows != C->h.ncols) throw Error(CPK_ERR_DIM, "A and C must be square");
-    if (A->h.nrows != M->p->gn || C->h.nrows != M->p->gm) throw Error(CPK_ERR_DIM, "A, C and M dimensions disagree");
-}
-
 static void check_dist_method(const Ctx &, int) {}
 
 int cpk_method_solve_device(cpk_ctx ctx, int method, const double *d_b, cpk_mat A, cpk_mat C, cpk_pc M,
@@ -957,20 +708,6 @@ int cpk_method_solve(cpk_ctx ctx, int method, const double *b, cpk_mat A, cpk_ma
     if (p.gm) std::memcpy(y, g.data() + p.gn, p.gm * sizeof(double));
     if (stats) stats->stime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     API_END
-}
-
-// the shift's two products: 1 GPU reads rows < n of blkdiag(A, C) and of Kp (columns >= n);
-// distributed mode has dedicated x-part row slices of [A 0] and [0 B']
-struct ShiftOps {
-    const DMat *A, *Bt;
-    int64_t bt_colmin;
-};
-static ShiftOps shift_ops(cpk_mat A, cpk_mat C, Precond &p) {
-    if (p.dist) {
-        auto pr = A->shift_ops(p);
-        return {pr.first, pr.second, 0};
-    }
-    return {&A->blkdiag_with(C), &p.dKp, p.n};
 }
 
 int cpk_reg_solve_device(cpk_ctx ctx, int method, const double *d_b, cpk_mat A, cpk_mat B, cpk_mat C, cpk_pc M,
@@ -1106,6 +843,8 @@ int cpk_reg_solve_op(cpk_ctx ctx, int method, const double *b, cpk_op A, cpk_mat
 }
 
 // ---- the saddle-point operator K = [A B'; B -C]: product, true residual, verified solve ----------
+// The drivers are kkt_driver.cpp's; an entry here checks (so a refusal writes nothing), stages and
+// copies back.
 int cpk_kkt_create(cpk_ctx ctx, cpk_mat A, cpk_mat B, cpk_mat C, cpk_kkt *out) {
     API_BEGIN
     need(ctx && A && B && C && out, "NULL argument");
@@ -1116,18 +855,7 @@ int cpk_kkt_create(cpk_ctx ctx, cpk_mat A, cpk_mat B, cpk_mat C, cpk_kkt *out) {
     auto k = std::make_unique<cpk_kkt_s>();
     k->ctx = ctx, k->A = A, k->B = B, k->C = C;
     k->n = A->h.nrows, k->m = C->h.nrows;
-    HCsr negC = C->host();
-    for (auto &v : negC.val) v = -v;
-    const HCsr &ha = A->host(), &hb = B->host();
-    make_dmat(assemble_kp(ha, hb, negC), k->K);
-    const std::vector<int64_t> ks = kp_value_sources(ha, hb, negC);
-    const int64_t off[3] = {0, ha.nnz(), ha.nnz() + hb.nnz()};
-    std::vector<uint32_t> src(ks.size());
-    for (size_t q = 0; q < ks.size(); q++) src[q] = (uint32_t)(off[ks[q] >> 40] + (ks[q] & ((int64_t(1) << 40) - 1)));
-    k->src.upload(src);
-    k->norms.alloc(8);
-    const cpk_mat_s *h[3] = {A, B, C};
-    for (int i = 0; i < 3; i++) k->gen[i] = h[i]->gen, k->vgen[i] = h[i]->vgen;
+    kkt_assemble(k.get());
     *out = k.release();
     API_END
 }
@@ -1150,7 +878,7 @@ int cpk_kkt_get_info(cpk_kkt K, int64_t info[8]) {
 int cpk_kkt_apply_device(cpk_kkt K, const double *d_z, double *d_y) {
     API_BEGIN
     need(K && ((d_z && d_y) || !(K->n + K->m)), "NULL argument");
-    launch_kkt_apply(K->ctx->c, K->current(), d_z, d_y);
+    kkt_apply(K, d_z, d_y);
     API_END
 }
 
@@ -1163,56 +891,10 @@ int cpk_kkt_apply(cpk_kkt K, const double *z, double *y) {
     DBuf<double> dz, dy;
     h2d(dz, z, (size_t)N);
     dy.alloc((size_t)N);
-    launch_kkt_apply(c, K->current(), dz.p, dy.p);
+    kkt_apply(K, dz.p, dy.p);
     CPK_HIP(hipMemcpyAsync(y, dy.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     CPK_HIP(hipStreamSynchronize(c.stream));
     API_END
-}
-
-// the checks of both residual entries; nothing is touched before they pass
-static void check_kkt_resid(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb,
-                            const double *R, int64_t ldr) {
-    need(K && Z && Bm, "NULL argument");
-    const int64_t N = K->n + K->m;
-    if (k < 0 || ldz < N || ldb < N || (R && ldr < N))
-        throw Error(CPK_ERR_DIM, "kkt_residual: k >= 0 and leading dimensions >= N required");
-}
-
-// Panels of kMultiKP columns.  A panel below the measured crossover (or with the loop forced) is a
-// loop of single-column passes.  Otherwise K is streamed once for the panel (kkt_panel_kernel: every
-// column's R in spmv_stream's row order) and each column's sums are taken from its r and b by
-// kkt_sums_kernel in the single-column pass's order -- so either path gives a column the same
-// bits, and the routing cannot change one.  r goes to a work array when the caller wants no R or
-// wants it over Bm (the sums read b after r exists), and is copied over Bm afterwards.
-static void kkt_resid_block(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_B, int64_t ldb,
-                            double *d_R, int64_t ldr, double *d_norms) {
-    const DMat &Kd = K->current();
-    Ctx &c = K->ctx->c;
-    const int64_t N = K->n + K->m;
-    if (!d_R && !d_norms) return;
-    for (int64_t j0 = 0; j0 < k; j0 += kMultiKP) {
-        const int kc = (int)std::min<int64_t>(kMultiKP, k - j0);
-        const bool panel = N > 0 && (K->route == 1 || (K->route == 0 && kc >= kKktPanelMinCols));
-        if (!panel) {
-            for (int64_t j = j0; j < j0 + kc; j++)
-                launch_kkt_resid(c, Kd, K->n, d_Z + j * ldz, d_B + j * ldb, d_R ? d_R + j * ldr : nullptr,
-                                 d_norms ? d_norms + 4 * j : nullptr);
-            continue;
-        }
-        const size_t pn = (size_t)N * kMultiKP;
-        const bool aside = !d_R || d_R == d_B;
-        if (aside && K->Tp.n < pn) K->Tp.alloc(pn);
-        double *dst = aside ? K->Tp.p : d_R + j0 * ldr;
-        const int64_t ldd = aside ? N : ldr;
-        launch_kkt_panel(c, Kd, kc, d_Z + j0 * ldz, ldz, d_B + j0 * ldb, ldb, dst, ldd);
-        if (d_norms)
-            for (int j = 0; j < kc; j++)
-                launch_kkt_sums(c, Kd, K->n, dst + j * ldd, d_B + (j0 + j) * ldb, d_norms + 4 * (j0 + j));
-        if (d_R && aside)
-            CPK_HIP(hipMemcpy2DAsync(d_R + j0 * ldr, (size_t)ldr * sizeof(double), dst, (size_t)ldd * sizeof(double),
-                                     (size_t)N * sizeof(double), (size_t)kc, hipMemcpyDeviceToDevice, c.stream));
-        K->panels++;
-    }
 }
 
 int cpk_kkt_set_route(cpk_kkt K, int route) {
@@ -1231,37 +913,43 @@ int cpk_kkt_route_info(cpk_kkt K, int64_t info[4]) {
     API_END
 }
 
-int cpk_kkt_residual_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
-                            double *d_R, int64_t ldr, double *d_norms) {
-    API_BEGIN
+// The residual entries, plain (kkt_resid_block) and exactly rounded (kkt_resid_exact_block), in
+// their three forms.  The checks of all of them; nothing is touched before they pass
+using ResidBlock = decltype(&kkt_resid_block);
+static void check_kkt_resid(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb,
+                            const double *R, int64_t ldr) {
+    need(K && Z && Bm, "NULL argument");
+    const int64_t N = K->n + K->m;
+    if (k < 0 || ldz < N || ldb < N || (R && ldr < N))
+        throw Error(CPK_ERR_DIM, "kkt_residual: k >= 0 and leading dimensions >= N required");
+}
+
+static void kkt_residual_device(ResidBlock block, cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm,
+                                int64_t ldb, double *d_R, int64_t ldr, double *d_norms) {
     check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
-    if (k == 0) return CPK_OK;
-    kkt_resid_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
-    API_END
+    if (k == 0) return;
+    block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
 }
 
 // device operands, the sums to HOST memory: they are taken in a device buffer, copied back and
 // waited for, so a caller without a device allocator (the Python class) can have them
-int cpk_kkt_residual_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
-                                 double *d_R, int64_t ldr, double *norms) {
-    API_BEGIN
+static void kkt_residual_device_sums(ResidBlock block, cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz,
+                                     const double *d_Bm, int64_t ldb, double *d_R, int64_t ldr, double *norms) {
     check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
     need(norms != nullptr, "NULL argument");
-    if (k == 0) return CPK_OK;
+    if (k == 0) return;
     Ctx &c = K->ctx->c;
     DBuf<double> dn;
     dn.alloc(4 * (size_t)k);
-    kkt_resid_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, dn.p);
+    block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, dn.p);
     CPK_HIP(hipMemcpyAsync(norms, dn.p, dn.bytes(), hipMemcpyDeviceToHost, c.stream));
     CPK_HIP(hipStreamSynchronize(c.stream));
-    API_END
 }
 
-int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
-                     int64_t ldr, double *norms) {
-    API_BEGIN
+static void kkt_residual_host(ResidBlock block, cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm,
+                              int64_t ldb, double *R, int64_t ldr, double *norms) {
     check_kkt_resid(K, k, Z, ldz, Bm, ldb, R, ldr);
-    if (k == 0) return CPK_OK;
+    if (k == 0) return;
     Ctx &c = K->ctx->c;
     const int64_t N = K->n + K->m;
     HostBlock dZ(N, k), dB(N, k);
@@ -1269,133 +957,50 @@ int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const d
     if (norms) dn.alloc(4 * (size_t)k);
     dZ.up(Z, ldz), dB.up(Bm, ldb);
     // in place on the staged right-hand sides: a row reads b_i before it writes r_i
-    kkt_resid_block(K, k, dZ.d.p, dZ.ld(), dB.d.p, dB.ld(), R ? dB.d.p : nullptr, dB.ld(), dn.p);
+    block(K, k, dZ.d.p, dZ.ld(), dB.d.p, dB.ld(), R ? dB.d.p : nullptr, dB.ld(), dn.p);
     CPK_HIP(hipStreamSynchronize(c.stream));
     if (R) dB.down(R, ldr);
     if (norms) CPK_HIP(hipMemcpy(norms, dn.p, 4 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+int cpk_kkt_residual_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                            double *d_R, int64_t ldr, double *d_norms) {
+    API_BEGIN
+    kkt_residual_device(kkt_resid_block, K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
     API_END
 }
-
-// ---- the exactly rounded residual: cpk_kkt_residual's entries with r_i = RN(exact row sum) --------
-// A block is a loop of single-column passes (no panel kernel, no routing): launch_kkt_resid_exact
-// forms a column's r, kkt_sums_kernel takes its sums from the stored r and b in the single-column
-// pass's order, so they are what cpk_kkt_residual's sums would be on that r and b.  r goes to K's
-// work array when the caller wants no R or wants it over Bm (the sums read b after r exists).
-static void kkt_resid_exact_block(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_B, int64_t ldb,
-                                  double *d_R, int64_t ldr, double *d_norms) {
-    const DMat &Kd = K->current();
-    Ctx &c = K->ctx->c;
-    const int64_t N = K->n + K->m;
-    if (!d_R && !d_norms) return;
-    const bool aside = d_norms && (!d_R || d_R == d_B);
-    if (aside && K->Tp.n < (size_t)N) K->Tp.alloc((size_t)N * kMultiKP);  // the panel path's size
-    for (int64_t j = 0; j < k; j++) {
-        const double *b = d_B + j * ldb;
-        double *dst = aside ? K->Tp.p : d_R + j * ldr;
-        launch_kkt_resid_exact(c, Kd, d_Z + j * ldz, b, dst);
-        if (d_norms) launch_kkt_sums(c, Kd, K->n, dst, b, d_norms + 4 * j);
-        if (d_R && aside && N)
-            CPK_HIP(hipMemcpyAsync(d_R + j * ldr, dst, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-    }
+int cpk_kkt_residual_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
+                                 double *d_R, int64_t ldr, double *norms) {
+    API_BEGIN
+    kkt_residual_device_sums(kkt_resid_block, K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, norms);
+    API_END
 }
-
+int cpk_kkt_residual(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
+                     int64_t ldr, double *norms) {
+    API_BEGIN
+    kkt_residual_host(kkt_resid_block, K, k, Z, ldz, Bm, ldb, R, ldr, norms);
+    API_END
+}
 int cpk_kkt_residual_exact_device(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm, int64_t ldb,
                                   double *d_R, int64_t ldr, double *d_norms) {
     API_BEGIN
-    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
-    if (k == 0) return CPK_OK;
-    kkt_resid_exact_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
+    kkt_residual_device(kkt_resid_exact_block, K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, d_norms);
     API_END
 }
-
 int cpk_kkt_residual_exact_device_sums(cpk_kkt K, int64_t k, const double *d_Z, int64_t ldz, const double *d_Bm,
                                        int64_t ldb, double *d_R, int64_t ldr, double *norms) {
     API_BEGIN
-    check_kkt_resid(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr);
-    need(norms != nullptr, "NULL argument");
-    if (k == 0) return CPK_OK;
-    Ctx &c = K->ctx->c;
-    DBuf<double> dn;
-    dn.alloc(4 * (size_t)k);
-    kkt_resid_exact_block(K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, dn.p);
-    CPK_HIP(hipMemcpyAsync(norms, dn.p, dn.bytes(), hipMemcpyDeviceToHost, c.stream));
-    CPK_HIP(hipStreamSynchronize(c.stream));
+    kkt_residual_device_sums(kkt_resid_exact_block, K, k, d_Z, ldz, d_Bm, ldb, d_R, ldr, norms);
     API_END
 }
-
 int cpk_kkt_residual_exact(cpk_kkt K, int64_t k, const double *Z, int64_t ldz, const double *Bm, int64_t ldb, double *R,
                            int64_t ldr, double *norms) {
     API_BEGIN
-    check_kkt_resid(K, k, Z, ldz, Bm, ldb, R, ldr);
-    if (k == 0) return CPK_OK;
-    Ctx &c = K->ctx->c;
-    const int64_t N = K->n + K->m;
-    HostBlock dZ(N, k), dB(N, k);
-    DBuf<double> dn;
-    if (norms) dn.alloc(4 * (size_t)k);
-    dZ.up(Z, ldz), dB.up(Bm, ldb);
-    kkt_resid_exact_block(K, k, dZ.d.p, dZ.ld(), dB.d.p, dB.ld(), R ? dB.d.p : nullptr, dB.ld(), dn.p);
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    if (R) dB.down(R, ldr);
-    if (norms) CPK_HIP(hipMemcpy(norms, dn.p, 4 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+    kkt_residual_host(kkt_resid_exact_block, K, k, Z, ldz, Bm, ldb, R, ldr, norms);
     API_END
 }
 
-// cold: reg_cpkrylov's driver on b (cpk_reg_solve_device's call exactly).  warm: r = b - K*x0, the
-// same driver on r (its shift included, reg_cpkrylov.m:152-175), x = x0 + dx.  res (host, 8):
-// the four sums of the start residual, then those of b - K*x for the returned x.
-static void kkt_solve_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
-                           cpk_stats *stats, double *res) {
-    cpk_mat A = K->A, C = K->C;
-    need(M->ctx == K->ctx, "kkt_solve: M belongs to another context");
-    check_method_dims(A, C, M);
-    Ctx &c = K->ctx->c;
-    Precond &p = *M->p;
-    const int64_t N = K->n + K->m;
-    const DMat &Kd = K->current();
-    const DMat &AC = A->krylov_op(C, p);
-    const ShiftOps so = shift_ops(A, C, p);
-    double *dn = K->norms.p;
-    // the driver's vectors live in K, so every call hands the method the same addresses and finds
-    // the solver M cached under them (solver_key): [shift's three; warm residual; warm correction]
-    const size_t wsn = reg_solve_ws(N, K->n), part = reg_solve_ws_part(N);
-    if (K->ws.n < wsn + 2 * part) K->ws.alloc(wsn + 2 * part);
-    double *ws = K->ws.p;
-    if (stats) stats->ptime = p.ptime;  // also where the driver stops with its error
-    auto finish = [&] {
-        launch_kkt_resid(c, Kd, K->n, d_x, d_b, nullptr, dn + 4);
-        if (res) CPK_HIP(hipMemcpyAsync(res, dn, 8 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    };
-    if (!warm) {
-        // the start residual of x = 0 is b: its sums in the residual pass's order, K not streamed
-        if (N) CPK_HIP(hipMemsetAsync(d_x, 0, N * sizeof(double), c.stream));
-        launch_kkt_sums(c, Kd, K->n, d_b, d_b, dn);
-        try {
-            reg_solve_device(c, method, d_b, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_x, stats, nullptr, ws);
-        } catch (...) {
-            finish();
-            throw;
-        }
-    } else {
-        double *r = ws + wsn, *dx = r + part;
-        CPK_HIP(hipMemsetAsync(dx, 0, (size_t)std::max<int64_t>(N, 1) * sizeof(double), c.stream));
-        launch_kkt_resid(c, Kd, K->n, d_x, d_b, r, dn);
-        std::exception_ptr err;
-        try {
-            reg_solve_device(c, method, r, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dx, stats, nullptr, ws);
-        } catch (...) {
-            err = std::current_exception();
-        }
-        launch_recover(c, N, d_x, dx, d_x);  // x0 plus whatever the driver wrote
-        if (err) {
-            finish();
-            std::rethrow_exception(err);
-        }
-    }
-    finish();
-}
-
+// ---- the verified solve, the refined solve and the adjoint: host forms by host_column_solve ------
 int cpk_kkt_solve_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
                          cpk_stats *stats, double *res) {
     API_BEGIN
@@ -1408,99 +1013,10 @@ int cpk_kkt_solve(cpk_kkt K, int method, const double *b, cpk_pc M, const cpk_op
                   cpk_stats *stats, double *res) {
     API_BEGIN
     need(K && M && ((b && x) || !(K->n + K->m)), "NULL argument");
-    Ctx &c = K->ctx->c;
-    const int64_t N = K->n + K->m;
-    DBuf<double> db, dx;
-    h2d(db, b, (size_t)N);
-    if (warm) h2d(dx, x, (size_t)N);
-    else dx.alloc((size_t)std::max<int64_t>(N, 1));
-    std::exception_ptr err;
-    try {
-        kkt_solve_core(K, method, db.p, M, opts, dx.p, warm, stats, res);
-    } catch (...) {
-        err = std::current_exception();
-    }
-    if (N) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    if (err) std::rethrow_exception(err);
+    host_column_solve(K->ctx->c.stream, K->n + K->m, b, x, warm, nullptr, nullptr, [&](const double *d_b, double *d_x) {
+        kkt_solve_core(K, method, d_b, M, opts, d_x, warm, stats, res);
+    });
     API_END
-}
-
-// ---- iterative refinement on the exactly rounded residual (cpk_kkt_solve_refined) ----------------
-// x_0 = x0 (warm) or 0; driver call j = 0 .. max_steps runs reg_solve_device on r_j = the exactly
-// rounded b - K*x_j (cold, j = 0: on b itself, which that residual is) from a zero start and gives
-// the trial x_j + dx_j, one rounding per entry.  r_{j+1} is formed at the trial: unless its sum of
-// squares is below r_j's the trial is dropped and the loop ends with x_j; the last call's trial
-// (j = max_steps) is taken as cpk_kkt_solve takes its own, without a further residual.  A driver
-// error ends the loop with x_j plus whatever the driver wrote.  The driver's vectors, r, dx and the
-// trial live in K (kkt_solve_core's layout plus the trial), at the same addresses on every call.
-static void kkt_refined_core(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x, int warm,
-                             int max_steps, cpk_stats *stats, double *res, int *steps_out, bool *wrote_x = nullptr) {
-    cpk_mat A = K->A, C = K->C;
-    need(M->ctx == K->ctx, "kkt_solve_refined: M belongs to another context");
-    check_method_dims(A, C, M);
-    Ctx &c = K->ctx->c;
-    Precond &p = *M->p;
-    const int64_t N = K->n + K->m;
-    const DMat &Kd = K->current();
-    const DMat &AC = A->krylov_op(C, p);
-    const ShiftOps so = shift_ops(A, C, p);
-    double *dn = K->norms.p;
-    const size_t wsn = reg_solve_ws(N, K->n), part = reg_solve_ws_part(N), nb = (size_t)N * sizeof(double);
-    if (K->ws.n < wsn + 3 * part) K->ws.alloc(wsn + 3 * part);
-    double *ws = K->ws.p, *r = ws + wsn, *dx = r + part, *xt = dx + part;
-    if (stats) stats->ptime = p.ptime;
-    if (steps_out) *steps_out = 0;
-    if (wrote_x) *wrote_x = true;  // every refusal is behind us: from here on d_x holds an iterate
-    // the four sums of residual `row` (rv against b), to res; returns sum r^2
-    auto sums = [&](const double *rv, int row) {
-        double h[4];
-        launch_kkt_sums(c, Kd, K->n, rv, d_b, dn);
-        CPK_HIP(hipMemcpyAsync(h, dn, sizeof h, hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-        if (res) std::memcpy(res + 4 * (size_t)row, h, sizeof h);
-        return h[0] + h[1];
-    };
-    auto take_trial = [&] {
-        if (N) CPK_HIP(hipMemcpyAsync(d_x, xt, nb, hipMemcpyDeviceToDevice, c.stream));
-    };
-    double rr;
-    if (!warm) {
-        if (N) CPK_HIP(hipMemsetAsync(d_x, 0, nb, c.stream));
-        rr = sums(d_b, 0);  // the start residual of x = 0 is b
-    } else {
-        launch_kkt_resid_exact(c, Kd, d_x, d_b, r);
-        rr = sums(r, 0);
-    }
-    int applied = 0;
-    for (int j = 0; j <= max_steps; j++) {
-        const bool on_b = !warm && j == 0;
-        double *out = on_b ? xt : dx;
-        CPK_HIP(hipMemsetAsync(out, 0, (size_t)std::max<int64_t>(N, 1) * sizeof(double), c.stream));
-        std::exception_ptr err;
-        try {
-            reg_solve_device(c, method, on_b ? d_b : r, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, out, stats, nullptr, ws);
-        } catch (...) {
-            err = std::current_exception();
-        }
-        if (!on_b) launch_recover(c, N, d_x, dx, xt);
-        if (err || j == max_steps) {
-            take_trial();
-            applied++;
-            CPK_HIP(hipStreamSynchronize(c.stream));
-            if (steps_out) *steps_out = applied - 1;
-            if (err) std::rethrow_exception(err);
-            return;
-        }
-        launch_kkt_resid_exact(c, Kd, xt, d_b, r);
-        const double rn = sums(r, j + 1);
-        if (!(rn < rr)) break;  // no decrease (or a NaN): this dx is not applied
-        take_trial();
-        applied++;
-        rr = rn;
-    }
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    if (steps_out) *steps_out = applied - 1;
 }
 
 int cpk_kkt_solve_refined_device(cpk_kkt K, int method, const double *d_b, cpk_pc M, const cpk_opts *opts, double *d_x,
@@ -1517,63 +1033,29 @@ int cpk_kkt_solve_refined(cpk_kkt K, int method, const double *b, cpk_pc M, cons
     API_BEGIN
     need(K && M && ((b && x) || !(K->n + K->m)), "NULL argument");
     need(max_steps >= 0, "kkt_solve_refined: max_steps >= 0 required");
-    Ctx &c = K->ctx->c;
-    const int64_t N = K->n + K->m;
-    DBuf<double> db, dx;
-    h2d(db, b, (size_t)N);
-    if (warm) h2d(dx, x, (size_t)N);
-    else dx.alloc((size_t)std::max<int64_t>(N, 1));
-    std::exception_ptr err;
     bool wrote_x = false;  // a refusal leaves the caller's x as it is
-    try {
-        kkt_refined_core(K, method, db.p, M, opts, dx.p, warm, max_steps, stats, res, steps_out, &wrote_x);
-    } catch (...) {
-        err = std::current_exception();
-    }
-    if (N && wrote_x) CPK_HIP(hipMemcpyAsync(x, dx.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    if (err) std::rethrow_exception(err);
+    host_column_solve(K->ctx->c.stream, K->n + K->m, b, x, warm, &wrote_x, nullptr, [&](const double *d_b, double *d_x) {
+        kkt_refined_core(K, method, d_b, M, opts, d_x, warm, max_steps, stats, res, steps_out, &wrote_x);
+    });
     API_END
 }
 
-// ---- the adjoint of the verified solve: lambda = K' \ gx, then the value gradients sampled on K's
-// own handles (adjoint.hip).  The checks first, so a refusal writes nothing; a stop inside the driver
-// leaves through kkt_solve_core's exception before any gradient pass is enqueued.
-static void check_kkt_adjoint(cpk_kkt K, cpk_kkt KT, cpk_pc M, const double *x, const double *gx, const double *lam,
-                              const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC, int64_t cC) {
-    need(K && M && ((x && gx && lam) || !(K->n + K->m)), "NULL argument");
-    need(!KT || (KT->ctx == K->ctx && KT->n == K->n && KT->m == K->m), "kkt_adjoint: KT's dimensions differ from K's");
+// a gradient array's count is its handle's creating call's entry count (what: the entry's refusal)
+static void check_grad_counts(cpk_kkt K, const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC,
+                              int64_t cC, const char *what) {
     const cpk_mat_s *h[3] = {K->A, K->B, K->C};
     const double *g[3] = {gA, gB, gC};
     const int64_t cnt[3] = {cA, cB, cC};
     for (int i = 0; i < 3; i++)
-        if (g[i] && cnt[i] != h[i]->vm.count)
-            throw Error(CPK_ERR_DIM, "kkt_adjoint: a gradient's count differs from its handle's creating call's entry count");
+        if (g[i] && cnt[i] != h[i]->vm.count) throw Error(CPK_ERR_DIM, what);
 }
 
-// d_x, d_lam: N device values each; d_g*: device arrays of the handles' entry counts (or null)
-static void kkt_adjoint_core(cpk_kkt K, cpk_kkt KT, int method, const double *d_x, const double *d_gx, cpk_pc M,
-                             const cpk_opts *opts, double *d_lam, int warm, double *d_gA, double *d_gB, double *d_gC,
-                             cpk_stats *stats, double *res) {
-    kkt_solve_core(KT ? KT : K, method, d_gx, M, opts, d_lam, warm, stats, res);
-    if (!d_gA && !d_gB && !d_gC) return;
-    Ctx &c = K->ctx->c;
-    const int64_t n = K->n;
-    // gB's two terms pair x with lambda both ways, U = [lambda_y, x_y] and V = [x_x, lambda_x]: the
-    // second column of each lies in the other vector, so the kernel's column stride is the distance
-    // between the two vectors in doubles, positive for one operand and negative for the other (two
-    // device arrays of doubles; the launcher takes any stride, the public entries only ld >= rows)
-    const int64_t lam_to_x = ((int64_t)(intptr_t)d_x - (int64_t)(intptr_t)d_lam) / (int64_t)sizeof(double);
-    auto pass = [&](cpk_mat_s *H, int64_t k, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
-                    double *out) {
-        if (!out) return;
-        const DMat &d = H->dev();
-        upload_value_map(H->vm, H->dvm);
-        launch_sample_outer(c, d, H->vm, H->dvm, k, U, ldu, V, ldv, alpha, out);
-    };
-    pass(K->A, 1, d_lam, 0, d_x, 0, -1.0, d_gA);                          // -lambda_x * x_x'
-    pass(K->B, 2, d_lam + n, lam_to_x, d_x, -lam_to_x, -1.0, d_gB);       // -(lambda_y * x_x' + x_y * lambda_x')
-    pass(K->C, 1, d_lam + n, 0, d_x + n, 0, 1.0, d_gC);                   // +lambda_y * x_y' (K holds -C)
+static void check_kkt_adjoint(cpk_kkt K, cpk_kkt KT, cpk_pc M, const double *x, const double *gx, const double *lam,
+                              const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC, int64_t cC) {
+    need(K && M && ((x && gx && lam) || !(K->n + K->m)), "NULL argument");
+    need(!KT || (KT->ctx == K->ctx && KT->n == K->n && KT->m == K->m), "kkt_adjoint: KT's dimensions differ from K's");
+    check_grad_counts(K, gA, cA, gB, cB, gC, cC,
+                      "kkt_adjoint: a gradient's count differs from its handle's creating call's entry count");
 }
 
 int cpk_kkt_adjoint_device(cpk_kkt K, cpk_kkt KT, int method, const double *d_x, const double *d_gx, cpk_pc M,
@@ -1591,30 +1073,13 @@ int cpk_kkt_adjoint(cpk_kkt K, cpk_kkt KT, int method, const double *x, const do
                     cpk_stats *stats, double *res) {
     API_BEGIN
     check_kkt_adjoint(K, KT, M, x, gx, lam, gA, cA, gB, cB, gC, cC);
-    Ctx &c = K->ctx->c;
     const int64_t N = K->n + K->m;
-    DBuf<double> dx, dgx, dlam, dg[3];
-    h2d(dx, x, (size_t)N), h2d(dgx, gx, (size_t)N);
-    if (warm) h2d(dlam, lam, (size_t)N);
-    else dlam.alloc((size_t)std::max<int64_t>(N, 1));
-    double *g[3] = {gA, gB, gC};
-    const int64_t cnt[3] = {cA, cB, cC};
-    for (int i = 0; i < 3; i++)
-        if (g[i]) dg[i].alloc((size_t)std::max<int64_t>(cnt[i], 1));
-    std::exception_ptr err;
-    try {
-        kkt_adjoint_core(K, KT, method, dx.p, dgx.p, M, opts, dlam.p, warm, g[0] ? dg[0].p : nullptr,
-                         g[1] ? dg[1].p : nullptr, g[2] ? dg[2].p : nullptr, stats, res);
-    } catch (...) {
-        err = std::current_exception();
-    }
-    if (N) CPK_HIP(hipMemcpyAsync(lam, dlam.p, N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    if (!err)
-        for (int i = 0; i < 3; i++)
-            if (g[i] && cnt[i])
-                CPK_HIP(hipMemcpyAsync(g[i], dg[i].p, (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    if (err) std::rethrow_exception(err);
+    DBuf<double> dx;  // the second input; gx is the solve's right-hand side, lam its x
+    h2d(dx, x, (size_t)N);
+    HostGrads g(gA, cA, gB, cB, gC, cC);
+    host_column_solve(K->ctx->c.stream, N, gx, lam, warm, nullptr, &g, [&](const double *d_gx, double *d_lam) {
+        kkt_adjoint_core(K, KT, method, dx.p, d_gx, M, opts, d_lam, warm, g.dev(0), g.dev(1), g.dev(2), stats, res);
+    });
     API_END
 }
 
@@ -1711,10 +1176,7 @@ int cpk_reg_solve_multi(cpk_ctx ctx, int method, int64_t k, const double *Bh, in
     API_END
 }
 
-// ---- the block forms of the verified solve and of its adjoint --------------------------------------
-// Column j is cpk_kkt_solve on B(:, j): the driver is reg_solve_multi_device unchanged (no routing by
-// k), the start sums are launch_kkt_sums of b_j (cold) or the block residual's (warm), the last four
-// those of one block residual of the returned X.  The checks first, so a refusal writes nothing.
+// ---- the block forms of the verified solve and of its adjoint: the checks first ------------------
 static void check_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double *B, int64_t ldb, cpk_pc M, const double *X,
                                   int64_t ldx) {
     need(K && M && ((B && X) || !(K->n + K->m)), "NULL argument");
@@ -1724,51 +1186,6 @@ static void check_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double
     need(M->ctx == K->ctx, "kkt_solve_multi: M belongs to another context");
     check_method_dims(K->A, K->C, M);
     require_block_solve(K->ctx->c, *M->p, method);
-}
-
-// res: host, 8 k (or null).  Returns CPK_OK or the first failing column's status (message in *msg)
-static int kkt_solve_multi_core(cpk_kkt K, int method, int64_t k, const double *d_B, int64_t ldb, cpk_pc M,
-                                const cpk_opts *opts, double *d_X, int64_t ldx, int warm, cpk_stats *stats, int *col_status,
-                                double *res, std::string *msg) {
-    if (k == 0) return CPK_OK;
-    cpk_mat A = K->A, C = K->C;
-    Ctx &c = K->ctx->c;
-    Precond &p = *M->p;
-    const int64_t N = K->n + K->m, N1 = std::max<int64_t>(N, 1);
-    const DMat &Kd = K->current();
-    const DMat &AC = A->krylov_op(C, p);
-    const ShiftOps so = shift_ops(A, C, p);
-    // [8 k: the call's sums, column by column; 4 k: a block residual's sums before they are spread]
-    if (K->normsb.n < 12 * (size_t)k) K->normsb.alloc(12 * (size_t)k);
-    double *dn = K->normsb.p, *dt = dn + 8 * k;
-    auto spread = [&](int at) {  // dt[4 j ..] -> dn[8 j + at ..]
-        CPK_HIP(hipMemcpy2DAsync(dn + at, 8 * sizeof(double), dt, 4 * sizeof(double), 4 * sizeof(double), (size_t)k,
-                                 hipMemcpyDeviceToDevice, c.stream));
-    };
-    int rc;
-    if (!warm) {
-        for (int64_t j = 0; j < k; j++) {
-            if (N) CPK_HIP(hipMemsetAsync(d_X + j * ldx, 0, N * sizeof(double), c.stream));
-            launch_kkt_sums(c, Kd, K->n, d_B + j * ldb, d_B + j * ldb, dn + 8 * j);
-        }
-        rc = reg_solve_multi_device(c, method, k, d_B, ldb, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, d_X, ldx, stats,
-                                    col_status, msg);
-    } else {
-        const size_t blk = (size_t)N1 * (size_t)k;
-        if (K->wsb.n < 2 * blk) K->wsb.alloc(2 * blk);
-        double *R = K->wsb.p, *dX = R + blk;
-        CPK_HIP(hipMemsetAsync(dX, 0, blk * sizeof(double), c.stream));
-        kkt_resid_block(K, k, d_X, ldx, d_B, ldb, R, N1, dt);
-        spread(0);
-        rc = reg_solve_multi_device(c, method, k, R, N1, AC, *so.A, *so.Bt, so.bt_colmin, p, opts, dX, N1, stats, col_status,
-                                    msg);
-        for (int64_t j = 0; j < k; j++) launch_recover(c, N, d_X + j * ldx, dX + j * N1, d_X + j * ldx);
-    }
-    kkt_resid_block(K, k, d_X, ldx, d_B, ldb, nullptr, 0, dt);
-    spread(4);
-    if (res) CPK_HIP(hipMemcpyAsync(res, dn, 8 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    CPK_HIP(hipStreamSynchronize(c.stream));
-    return rc;
 }
 
 int cpk_kkt_solve_multi_device(cpk_kkt K, int method, int64_t k, const double *d_B, int64_t ldb, cpk_pc M,
@@ -1799,83 +1216,15 @@ int cpk_kkt_solve_multi(cpk_kkt K, int method, int64_t k, const double *B, int64
     API_END
 }
 
-// The three gradient passes of a block: X and Lam (N x k) onto the sparsity of K's handles.  From
-// kSamplePanelMinCols columns the interleaved panels and the panel kernel (adjoint.hip); k = 1 is the
-// single-column adjoint's three launches, k = 0 writes alpha * 0.0
 static void check_kkt_sample(cpk_kkt K, int64_t k, const double *X, int64_t ldx, const double *L, int64_t ldl,
                              const double *gA, int64_t cA, const double *gB, int64_t cB, const double *gC, int64_t cC) {
     need(K && ((X && L) || !(K->n + K->m) || k == 0), "NULL argument");
     const int64_t N = K->n + K->m;
     if (k < 0 || k > INT32_MAX / 2 || ldx < N || ldl < N)
         throw Error(CPK_ERR_DIM, "kkt_sample_multi: k >= 0 and leading dimensions >= N required");
-    const cpk_mat_s *h[3] = {K->A, K->B, K->C};
-    const double *g[3] = {gA, gB, gC};
-    const int64_t cnt[3] = {cA, cB, cC};
-    for (int i = 0; i < 3; i++)
-        if (g[i] && cnt[i] != h[i]->vm.count)
-            throw Error(CPK_ERR_DIM, "kkt_sample_multi: a gradient's count differs from its handle's creating call's entry count");
+    check_grad_counts(K, gA, cA, gB, cB, gC, cC,
+                      "kkt_sample_multi: a gradient's count differs from its handle's creating call's entry count");
     if (K->ctx->c.dist()) throw Error(CPK_ERR_UNSUPPORTED, "kkt_sample_multi: single-GPU only");
-}
-
-static void kkt_sample_core(cpk_kkt K, int64_t k, const double *d_X, int64_t ldx, const double *d_L, int64_t ldl,
-                            double *d_gA, double *d_gB, double *d_gC) {
-    if (!d_gA && !d_gB && !d_gC) return;
-    Ctx &c = K->ctx->c;
-    const int64_t n = K->n, N = K->n + K->m;
-    auto dev = [&](cpk_mat_s *H) -> const DMat & {
-        const DMat &d = H->dev();
-        upload_value_map(H->vm, H->dvm);
-        return d;
-    };
-    // k < 2 has no panel path; from there the measured rule (or the forced route) decides, and either
-    // path gives every entry the same bits
-    const bool panel = k >= 2 && (K->sample_route == 1 || (K->sample_route == 0 && sample_panel_rule(k)));
-    if (!panel) {
-        auto pass = [&](cpk_mat_s *H, int64_t kk, const double *U, int64_t ldu, const double *V, int64_t ldv, double alpha,
-                        double *out) {
-            if (out) launch_sample_outer(c, dev(H), H->vm, H->dvm, kk, U, ldu, V, ldv, alpha, out);
-        };
-        pass(K->A, k, d_L, ldl, d_X, ldx, -1.0, d_gA);
-        pass(K->C, k, d_L + n, ldl, d_X + n, ldx, 1.0, d_gC);
-        if (!d_gB) return;
-        if (k <= 1) {
-            // gB's 2 k columns alternate between the two blocks (kkt_adjoint_core): for one column that
-            // is a column stride from Lam to X and back
-            const int64_t l2x = ((int64_t)(intptr_t)d_X - (int64_t)(intptr_t)d_L) / (int64_t)sizeof(double);
-            pass(K->B, 2 * k, d_L + n, l2x, d_X, -l2x, -1.0, d_gB);
-            return;
-        }
-        // for more columns one stride cannot express the alternation: the 2 k columns
-        // U = [ly_0, xy_0, ly_1, ...] (m rows) and V = [xx_0, lx_0, xx_1, ...] (n rows) are staged by
-        // four strided copies
-        const int64_t m = K->m, m1 = std::max<int64_t>(m, 1), n1 = std::max<int64_t>(n, 1);
-        const size_t need_d = 2 * (size_t)k * (size_t)(m1 + n1);
-        if (K->panel_ops.n < need_d) K->panel_ops.alloc(need_d);
-        double *U = K->panel_ops.p, *V = U + 2 * (size_t)k * (size_t)m1;
-        auto stage = [&](double *dst, int64_t ldd, const double *src, int64_t lds, int64_t rows) {
-            if (rows)
-                CPK_HIP(hipMemcpy2DAsync(dst, 2 * (size_t)ldd * sizeof(double), src, (size_t)lds * sizeof(double),
-                                         (size_t)rows * sizeof(double), (size_t)k, hipMemcpyDeviceToDevice, c.stream));
-        };
-        stage(U, m1, d_L + n, ldl, m), stage(U + m1, m1, d_X + n, ldx, m);
-        stage(V, n1, d_X, ldx, n), stage(V + n1, n1, d_L, ldl, n);
-        pass(K->B, 2 * k, U, m1, V, n1, -1.0, d_gB);
-        return;
-    }
-    K->sample_panels++;
-    const int64_t ps = N * kMultiKP;  // one panel of an array
-    const size_t per = (size_t)panel_count(k) * (size_t)ps;
-    if (K->panel_ops.n < 2 * per) K->panel_ops.alloc(2 * per);
-    double *PX = K->panel_ops.p, *PL = PX + per;
-    launch_pack_panels(c, N, k, d_X, ldx, d_L, ldl, PX, PL);
-    const double *xx = PX, *xy = PX + n * kMultiKP, *lx = PL, *ly = PL + n * kMultiKP;
-    auto pass = [&](cpk_mat_s *H, const double *U1, const double *V1, const double *U2, const double *V2, double alpha,
-                    double *out) {
-        if (out) launch_sample_panel(c, dev(H), H->vm, H->dvm, k, ps, U1, V1, U2, V2, alpha, out);
-    };
-    pass(K->A, lx, xx, nullptr, nullptr, -1.0, d_gA);  // -sum_c lx_c * xx_c'
-    pass(K->B, ly, xx, xy, lx, -1.0, d_gB);            // -sum_c (ly_c * xx_c' then xy_c * lx_c')
-    pass(K->C, ly, xy, nullptr, nullptr, 1.0, d_gC);   // +sum_c ly_c * xy_c' (K holds -C)
 }
 
 int cpk_kkt_set_sample_route(cpk_kkt K, int route) {
@@ -1903,35 +1252,16 @@ int cpk_kkt_sample_multi_device(cpk_kkt K, int64_t k, const double *d_X, int64_t
     API_END
 }
 
-// the gradient arrays of a host entry on the device, and back
-struct HostGrads {
-    DBuf<double> d[3];
-    double *h[3];
-    int64_t cnt[3];
-    HostGrads(double *gA, int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC) : h{gA, gB, gC}, cnt{cA, cB, cC} {
-        for (int i = 0; i < 3; i++)
-            if (h[i]) d[i].alloc((size_t)std::max<int64_t>(cnt[i], 1));
-    }
-    double *dev(int i) { return h[i] ? d[i].p : nullptr; }
-    void down(Ctx &c) {
-        for (int i = 0; i < 3; i++)
-            if (h[i] && cnt[i])
-                CPK_HIP(hipMemcpyAsync(h[i], d[i].p, (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        CPK_HIP(hipStreamSynchronize(c.stream));
-    }
-};
-
 int cpk_kkt_sample_multi(cpk_kkt K, int64_t k, const double *X, int64_t ldx, const double *Lam, int64_t ldl, double *gA,
                          int64_t cA, double *gB, int64_t cB, double *gC, int64_t cC) {
     API_BEGIN
     check_kkt_sample(K, k, X, ldx, Lam, ldl, gA, cA, gB, cB, gC, cC);
     const int64_t N = K->n + K->m;
-    HostBlock dX(N, std::max<int64_t>(k, 1)), dL(N, std::max<int64_t>(k, 1));
-    dX.k = dL.k = k;
-    if (k) dX.up(X, ldx), dL.up(Lam, ldl);
+    HostBlock dX(N, k), dL(N, k);
+    dX.up(X, ldx), dL.up(Lam, ldl);
     HostGrads g(gA, cA, gB, cB, gC, cC);
     kkt_sample_core(K, k, dX.d.p, dX.ld(), dL.d.p, dL.ld(), g.dev(0), g.dev(1), g.dev(2));
-    g.down(K->ctx->c);
+    g.down(K->ctx->c.stream);
     API_END
 }
 
@@ -1964,19 +1294,18 @@ int cpk_kkt_adjoint_multi(cpk_kkt K, int method, int64_t k, const double *X, int
                           double *gB, int64_t cB, double *gC, int64_t cC, cpk_stats *stats, int *col_status, double *res) {
     API_BEGIN
     check_kkt_adjoint_multi(K, method, k, X, ldx, GX, ldg, M, Lam, ldl, gA, cA, gB, cB, gC, cC);
-    const int64_t N = K->n + K->m, k1 = std::max<int64_t>(k, 1);
-    HostBlock dX(N, k1), dG(N, k1), dL(N, k1);
-    dX.k = dG.k = dL.k = k;
-    if (k) dX.up(X, ldx), dG.up(GX, ldg);
-    if (k && warm) dL.up(Lam, ldl);
+    const int64_t N = K->n + K->m;
+    HostBlock dX(N, k), dG(N, k), dL(N, k);
+    dX.up(X, ldx), dG.up(GX, ldg);
+    if (warm) dL.up(Lam, ldl);
     HostGrads g(gA, cA, gB, cB, gC, cC);
     std::string msg;
     const int rc = kkt_solve_multi_core(K, method, k, dG.d.p, dG.ld(), M, opts, dL.d.p, dL.ld(), warm, stats, col_status, res,
                                         &msg);
-    if (k) dL.down(Lam, ldl);
+    dL.down(Lam, ldl);
     if (rc != CPK_OK) return solve_multi_result(rc, msg);
     kkt_sample_core(K, k, dX.d.p, dX.ld(), dL.d.p, dL.ld(), g.dev(0), g.dev(1), g.dev(2));
-    g.down(K->ctx->c);
+    g.down(K->ctx->c.stream);
     API_END
 }
 

@@ -821,7 +821,7 @@ struct Precond {
     // preconditioner so far, evicted ones included (cpk_pc_solver_info)
     int64_t graph_inst = 0, block_graph_inst = 0;
     // distributed rows of the Krylov operator and the shift products, which follow this
-    // preconditioner's dof map (capi.cpp): keyed by (kind, matrix generation(s)); they die with it
+    // preconditioner's dof map (handles.hpp): keyed by (kind, matrix generation(s)); they die with it
     std::map<std::tuple<char, uint64_t, uint64_t>, std::unique_ptr<DMat>> dist_ops;
     // y = M*x  (opLDL2.multiply); all pointers on the device, enqueued on ctx->stream
     // piggy_src (distributed only, piggyback_ok()): kSepPiggy device values appended to the first
@@ -893,7 +893,7 @@ Precond *precond_create(Ctx &c, const HCsr &A11, const HCsr &B, const HCsr &C22)
 // with: Kp and the numeric factorization on the device, symbolic analysis reused; returns seconds
 double precond_refactor(Precond &p, const DMat &A11, const DMat &B, const DMat &C22);
 // = pattern_hash_combine of the three matrices' pattern_hash_one: a handle's sparsity never
-// changes, so the C ABI hashes each matrix once per handle (capi.cpp)
+// changes, so the C ABI hashes each matrix once per handle (handles.hpp)
 uint64_t pattern_hash(const HCsr &A11, const HCsr &B, const HCsr &C22);
 uint64_t pattern_hash_one(const HCsr &a);
 uint64_t pattern_hash_combine(uint64_t a11, uint64_t b, uint64_t c22);

@@ -10,7 +10,7 @@
 // residual.  A row reads b_i (Epi::pre) before it writes r_i, so r may overwrite b.
 // A block of columns can take the panel path instead: kkt_panel_kernel forms R for up to 8 columns
 // with K streamed once, and kkt_sums_kernel takes each column's sums from its r and b in the
-// single-column pass's order, so a column has the same bits on either path (capi.cpp routes).
+// single-column pass's order, so a column has the same bits on either path (kkt_driver.cpp routes).
 // kkt_resid_exact_kernel forms the exactly rounded residual (cpk_kkt_residual_exact): the exact row
 // sum rounded once, whose sums of squares kkt_sums_kernel then takes from the stored r.
 #include <hip/hip_runtime.h>
