@@ -1374,6 +1374,8 @@ int cpk_debug_arnoldi_step(cpk_ctx ctx, cpk_arnoldi_step *io) {
     need(s.kk >= 1 && (dq || s.kk <= s.win), "debug_arnoldi_step: kk >= 1 (cpgmres: kk <= restart) required");
     need(s.grid >= 0, "debug_arnoldi_step: grid >= 0 required");
     need(s.ldv >= s.N && (!dq || s.ldpv >= s.N), "debug_arnoldi_step: leading dimensions >= N required");
+    if (ctx->c.opts.basis_f32 && ctx->c.dist())  // before any device call, like the argument checks
+        throw Error(CPK_ERR_UNSUPPORTED, "engine option basis_f32: the Arnoldi step on a distributed context");
     const int64_t N = s.N, cols = s.win + 1;
     HostBlock dV(N, cols), dPV(N, dq ? cols : 1), dxy(N, 1), dw(N, 1), dut(N, 1);
     dV.up(s.V, s.ldv), dw.up(s.w, N), dut.up(s.ut, N);

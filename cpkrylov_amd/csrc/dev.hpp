@@ -100,7 +100,7 @@ struct SweepConfig {
 // (profiles/r04_dist_v3.txt: 815 it/s with the distributed default against 892 on one GPU).
 SweepConfig dist_sweep_default();
 
-// Engine options of a context (opts.cpp; cpk_ctx_set_option).  None but exact_dots and pivot_min
+// Engine options of a context (opts.cpp; cpk_ctx_set_option).  None but exact_dots, pivot_min and basis_f32
 // changes a result: they select equivalent execution paths (each is tested bit-exact against the default) or the
 // sweep schedule and the distributed split, which every rank must build identically -- so a
 // distributed preconditioner compares a hash of all of them across ranks before its first
@@ -151,6 +151,10 @@ struct EngineOpts {
                                   //                     of its TwoProd pairs (xacc.hpp): order-independent,
                                   //                     the oracle's orc_set_exact values bit for bit; the
                                   //                     one option that changes results (last bits)
+    bool basis_f32 = false;       // basis_f32:          cpgmres / cpdqgmres keep their basis and direction rings
+                                  //                     as float, each vector rounded once when it is stored,
+                                  //                     all arithmetic in double (DESIGN.md "Compressed basis");
+                                  //                     changes those two methods' results, nothing else
     int batch = 0;                // batch:              fixed iterations per graph (0: adaptive)
     bool profile_fwd_sched = false;     // profile_fwd_sched: diagnostic, the profiled forward reads its input in schedule order
     bool profile_passes = false;  // profile_passes:     diagnostic, cpdqgmres runs eagerly with HIP events around its

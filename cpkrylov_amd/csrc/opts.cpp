@@ -76,6 +76,7 @@ const BoolOpt kBool[] = {
     {"dist_graph", &EngineOpts::dist_graph},
     {"dist1", &EngineOpts::dist1},
     {"exact_dots", &EngineOpts::exact_dots},
+    {"basis_f32", &EngineOpts::basis_f32},
     {"no_chain", &EngineOpts::no_chain},
     {"no_bcast_analysis", &EngineOpts::no_bcast_analysis},
     {"apply_multi_panel", &EngineOpts::apply_multi_panel},

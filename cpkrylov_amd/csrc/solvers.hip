@@ -116,7 +116,11 @@ struct PolCgSpmv {
     }
 };
 
-// GMRES family: u = A*V_k; t = C*Q_k (no inner products needed)
+// GMRES family: u = A*V_k; t = C*Q_k (no inner products needed).  V is the double basis ring with
+// slots N apart.  Under engine option basis_f32 the ring holds floats, which the product cannot
+// read: the kernel that stores V_k also leaves it as doubles in the work vector VCUR, and the host
+// passes V = VCUR with N = 0, a stride of 0, so that every position selects VCUR
+// (SolveCore::arnoldi_pol; the type and its kernels are the double path's).
 struct PolArnoldiSpmv {
     static constexpr bool kNorm = false;
     const double *V;
@@ -928,6 +932,52 @@ struct CgDir {  // p = -r + beta*p; q = -t + beta*q
 };
 
 // ---- GMRES family --------------------------------------------------------------------------
+// The ring element type T of the basis V and of cpdqgmres's directions PV: double, or float under
+// engine option basis_f32 (DESIGN.md "Compressed basis").  Every kernel below that touches a ring
+// is a template on T and its double instantiation is the code as it was; what differs for float
+// sits behind `if constexpr`:
+//   * a ring read converts the float exactly to double, all arithmetic is double;
+//   * the vector under construction V_{k+1} lives in the double work vector VNEW (a fixed
+//     address) from the window dots to the normalisation, which rounds it once into its ring slot
+//     and writes the same rounded values as doubles to VCUR, the vector the next Krylov product
+//     multiplies (PolArnoldiSpmv with stride 0);
+//   * a slot's stride is padded to 64 floats, so every slot base is 256-byte aligned;
+//   * VNEW and VCUR sit behind the basis ring's last slot (ring_work), so the kernels take the
+//     arguments they always took.
+template <class T>
+constexpr bool kRingF32 = std::is_same<T, float>::value;
+template <class T>
+__host__ __device__ inline int64_t ring_ld(int64_t N) {
+    if constexpr (kRingF32<T>) return (N + 63) & ~(int64_t)63;
+    else return N;
+}
+// the float basis ring of nslots slots: VNEW = ring_work(...), VCUR = VNEW + ring_ld<float>(N)
+__host__ __device__ inline double *ring_work(float *V, int64_t nslots, int64_t N) {
+    return reinterpret_cast<double *>(V + nslots * ring_ld<float>(N));
+}
+// slots of the basis ring: cpdqgmres mem + 1 (`ring`), cpgmres (ring == 0) restart + 1
+__device__ inline int64_t ring_slots(const DState *st, int64_t ring) { return ring ? ring : st->restart + 1; }
+// V_1 under basis_f32: ArnoldiStart has left [w_x; (y) - w_y] in VNEW; normalise (NormalizeCopy's
+// rule for residNorm), round once into ring slot 0 and leave the rounded vector in VCUR
+struct NormalizeRound {
+    DState *st;
+    const double *vnew;
+    float *v1;
+    double *vcur;
+    double s;
+    __device__ bool setup() {
+        s = st->residNorm;
+        return true;
+    }
+    __device__ void operator()(int64_t i) {
+        double v = vnew[i];
+        if (s != 0) v = v / s;
+        const float r = (float)v;
+        v1[i] = r;
+        vcur[i] = (double)r;
+    }
+};
+
 // Start of a GMRES cycle / DQGMRES init:
 //   V1 = w(1:n); Q1 = (restart ? y : 0) - w(n+1:N); residNorm = sqrt(dot(u,V1) + dot(t,Q1))
 struct ArnoldiStart {
@@ -1011,16 +1061,30 @@ __device__ inline double &Hd(DState *st, int64_t j, int64_t kk) {  // H(j, kk), 
 #ifndef CPK_DOT_TILE
 #define CPK_DOT_TILE 3
 #endif
+#ifndef CPK_DOT_TILE_F32
+#define CPK_DOT_TILE_F32 (2 * CPK_DOT_TILE)
+#endif
 constexpr int kDotGroup = CPK_DOT_GROUP;
-constexpr int kDotTile = CPK_DOT_TILE;  // elements per thread per step, kBlock apart
-__global__ __launch_bounds__(kBlock) void arnoldi_dots_kernel(DState *st, double *V, const double *w,
+// elements per thread per step, kBlock apart.  The operands wait in registers as T, so a float
+// tile of twice the elements holds the same operand registers and the same bytes per wave as the
+// double one.  It does not hold the same bytes per CU: u[], the indices and the conversions grow
+// with the tile, and the float kernel resides with fewer waves (DESIGN.md "Compressed basis" has
+// the registers, the occupancies and the measured pass rates of the sizes tried).
+template <class T>
+constexpr int kDotTileOf = kRingF32<T> ? CPK_DOT_TILE_F32 : CPK_DOT_TILE;
+template <class T>
+__global__ __launch_bounds__(kBlock) void arnoldi_dots_kernel(DState *st, T *V, const double *w,
                                                               const double *ut, int64_t n, int64_t N, int64_t ring,
                                                               int64_t maxv, RedBuf rb) {
     if (!st->running) return;
+    constexpr int kDotTile = kDotTileOf<T>;
+    const int64_t ld = ring_ld<T>(N);
     const Window win = window(st, ring);
     const int64_t kk = win.kk;
-    double *vnew = V + (ring ? (kk % ring) : kk) * N;
-    const double *vk = V + win.slot(kk) * N;
+    double *vnew;
+    if constexpr (kRingF32<T>) vnew = ring_work(V, ring_slots(st, ring), N);
+    else vnew = V + (ring ? (kk % ring) : kk) * N;
+    const T *vk = V + win.slot(kk) * ld;
     // phase 0: new basis vector (fused with the first dot group).  A thread's indices grow, so
     // it meets the [x; y] boundary at most once: one accumulator per vector, whose x-part
     // sum is parked in accn when the thread crosses into the y-part (same additions, same
@@ -1029,9 +1093,9 @@ __global__ __launch_bounds__(kBlock) void arnoldi_dots_kernel(DState *st, double
         double acc[kDotGroup], accn[kDotGroup];
 #pragma unroll
         for (int j = 0; j < kDotGroup; j++) acc[j] = 0.0, accn[j] = 0.0;
-        const double *vj[kDotGroup];
+        const T *vj[kDotGroup];
 #pragma unroll
-        for (int j = 0; j < kDotGroup; j++) vj[j] = (g0 + j < win.nv) ? V + win.slot(win.jlo + g0 + j) * N : nullptr;
+        for (int j = 0; j < kDotGroup; j++) vj[j] = (g0 + j < win.nv) ? V + win.slot(win.jlo + g0 + j) * ld : nullptr;
         bool crossed = false;
         if (kDotTile == 1) {
             for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) {
@@ -1049,13 +1113,14 @@ __global__ __launch_bounds__(kBlock) void arnoldi_dots_kernel(DState *st, double
         } else {
             for (int64_t i0 = blockIdx.x * (int64_t)kBlock * kDotTile + threadIdx.x; i0 < N;
                  i0 += (int64_t)gridDim.x * kBlock * kDotTile) {
-                double u[kDotTile], x[kDotTile][kDotGroup];
+                double u[kDotTile];
+                T x[kDotTile][kDotGroup];
 #pragma unroll
                 for (int e = 0; e < kDotTile; e++) {
                     const int64_t i = min(i0 + e * kBlock, N - 1);  // clamped: loads need no predicate
                     u[e] = ut[i];
 #pragma unroll
-                    for (int j = 0; j < kDotGroup; j++) x[e][j] = vj[j] ? vj[j][i] : 0.0;
+                    for (int j = 0; j < kDotGroup; j++) x[e][j] = vj[j] ? vj[j][i] : T(0);
                 }
 #pragma unroll
                 for (int e = 0; e < kDotTile; e++) {
@@ -1137,23 +1202,27 @@ __global__ __launch_bounds__(kBlock) void arnoldi_dots_kernel(DState *st, double
 // sums in chunks of 16 (an even count: a window pair stays in one chunk).  Sum index
 // 2 * (window position) + (0: x-part, 1: y-part) of 2 * maxv per launch.
 constexpr int kXDotGroup = 4;
-__global__ __launch_bounds__(kBlock) void arnoldi_dots_exact_kernel(DState *st, double *V, const double *w,
+template <class T>
+__global__ __launch_bounds__(kBlock) void arnoldi_dots_exact_kernel(DState *st, T *V, const double *w,
                                                                     const double *ut, int64_t n, int64_t N,
                                                                     int64_t ring, int64_t maxv, RedBuf rb) {
     if (!st->running) return;
+    const int64_t ld = ring_ld<T>(N);
     const Window win = window(st, ring);
     const int64_t kk = win.kk;
-    double *vnew = V + (ring ? (kk % ring) : kk) * N;
-    const double *vk = V + win.slot(kk) * N;
+    double *vnew;
+    if constexpr (kRingF32<T>) vnew = ring_work(V, ring_slots(st, ring), N);
+    else vnew = V + (ring ? (kk % ring) : kk) * N;
+    const T *vk = V + win.slot(kk) * ld;
     const int nsum = (int)(2 * maxv);
     for (int64_t g0 = 0; g0 < win.nv; g0 += kXDotGroup) {
         XAcc acc[2 * kXDotGroup];  // [2q]: x-part of window vector g0 + q, [2q + 1]: y-part
-        const double *vj[kXDotGroup];
+        const T *vj[kXDotGroup];
 #pragma unroll
         for (int q = 0; q < kXDotGroup; q++) {
             acc_init(acc[2 * q], rb.xsub, (int)(2 * (g0 + q)) % nsum, nsum);
             acc_init(acc[2 * q + 1], rb.xsub, (int)(2 * (g0 + q) + 1) % nsum, nsum);
-            vj[q] = (g0 + q < win.nv) ? V + win.slot(win.jlo + g0 + q) * N : nullptr;
+            vj[q] = (g0 + q < win.nv) ? V + win.slot(win.jlo + g0 + q) * ld : nullptr;
         }
         for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) {
             const double u = ut[i];
@@ -1209,7 +1278,8 @@ __global__ void arnoldi_fin_kernel(DState *st, int64_t ring, const double *tot) 
 
 // the window dots of one Arnoldi step (with the distributed allreduce when needed)
 // grid_override: 0 for the solvers' own grid; cpk_debug_arnoldi_step passes another one (<= kEwGrid)
-static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, const double *ut, int64_t n, int64_t N,
+template <class T>
+static void launch_arnoldi_dots(Ctx &c, DState *st, T *V, const double *w, const double *ut, int64_t n, int64_t N,
                                 int64_t ring, int64_t maxv, int grid_override = 0) {
     const bool dist = c.dist();
     if (dist && (size_t)(2 * maxv) > c.red.n) throw Error(CPK_ERR_UNSUPPORTED, "Arnoldi window too wide for the distributed reduction buffer");
@@ -1217,7 +1287,7 @@ static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, 
     // would double the pass's tail (cf. spmv_grid)
     static const int resident = [] {
         int occ = 0, dev = 0, cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)arnoldi_dots_kernel, kBlock, 0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)arnoldi_dots_kernel<T>, kBlock, 0) != hipSuccess ||
             occ < 1)
             occ = 1;
         (void)hipGetDevice(&dev);
@@ -1226,10 +1296,10 @@ static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, 
     }();
     const int grid = grid_override > 0 ? std::min(grid_override, kEwGrid) : std::min(ew_grid(N), resident);
     if (c.exact())
-        hipLaunchKernelGGL(arnoldi_dots_exact_kernel, dim3(grid), dim3(kBlock), 0, c.stream, st, V, w, ut, n, N, ring,
+        hipLaunchKernelGGL(arnoldi_dots_exact_kernel<T>, dim3(grid), dim3(kBlock), 0, c.stream, st, V, w, ut, n, N, ring,
                            maxv, red_buf(c));
     else
-        hipLaunchKernelGGL(arnoldi_dots_kernel, dim3(grid), dim3(kBlock), 0, c.stream, st, V, w, ut, n, N, ring, maxv,
+        hipLaunchKernelGGL(arnoldi_dots_kernel<T>, dim3(grid), dim3(kBlock), 0, c.stream, st, V, w, ut, n, N, ring, maxv,
                            red_buf(c));
     if (dist) {
         allreduce_red(c, (int)(2 * maxv));
@@ -1243,29 +1313,41 @@ static void launch_arnoldi_dots(Ctx &c, DState *st, double *V, const double *w, 
 // the per-element loops then read (h_j, V_j) from LDS instead of recomputing ring slots and
 // H indices (64-bit divisions) for every element.
 constexpr int kWinTab = 1024;
+template <class T>
 struct WinTab {
-    const double *const *p;
+    const T *const *p;
     const double *h;
     int nv;
 };
+// window vectors whose loads one trip of a tiled window loop issues: 4 of kTile doubles; a float
+// load moves half the bytes, so 8 keep the same bytes per wave and trip (per CU the float kernels
+// reside with fewer waves: DESIGN.md "Compressed basis")
+#ifndef CPK_WIN_UNROLL_F32
+#define CPK_WIN_UNROLL_F32 8
+#endif
+template <class T>
+constexpr int kWinUnroll = kRingF32<T> ? CPK_WIN_UNROLL_F32 : 4;
 
+template <class T>
 struct ArnoldiOrth {
     DState *st;
-    double *V;
+    T *V;
     const double *ut;
     int64_t n, N, ring;
     Window win;
     double *vnew;
-    WinTab tab;
+    WinTab<T> tab;
     __device__ bool setup() {
         if (!st->running) return false;
         win = window(st, ring);
-        vnew = V + (ring ? (win.kk % ring) : win.kk) * N;
-        __shared__ const double *tp[kWinTab];
+        const int64_t ld = ring_ld<T>(N);
+        if constexpr (kRingF32<T>) vnew = ring_work(V, ring_slots(st, ring), N);
+        else vnew = V + (ring ? (win.kk % ring) : win.kk) * N;
+        __shared__ const T *tp[kWinTab];
         __shared__ double th[kWinTab];
         tab.nv = win.nv <= kWinTab ? (int)win.nv : -1;
         for (int j = threadIdx.x; j < tab.nv; j += blockDim.x) {
-            tp[j] = V + win.slot(win.jlo + j) * N;
+            tp[j] = V + win.slot(win.jlo + j) * ld;
             th[j] = h(win.jlo + j);
         }
         __syncthreads();
@@ -1282,7 +1364,7 @@ struct ArnoldiOrth {
 #pragma unroll 8
             for (int j = 0; j < tab.nv; j++) v = v - tab.h[j] * tab.p[j][i];
         } else {
-            for (int64_t j = win.jlo; j <= win.kk; j++) v = v - h(j) * V[win.slot(j) * N + i];
+            for (int64_t j = win.jlo; j <= win.kk; j++) v = v - h(j) * V[win.slot(j) * ring_ld<T>(N) + i];
         }
         vnew[i] = v;
         if (i < n) dadd(acc[0], ut[i], v);  // (no dynamic index: an XAcc array stays in registers)
@@ -1300,10 +1382,10 @@ struct ArnoldiOrth {
         double v[kTile];
 #pragma unroll
         for (int e = 0; e < kTile; e++) v[e] = vnew[i0 + e * kBlock];
-#pragma unroll 4
+#pragma unroll kWinUnroll<T>
         for (int j = 0; j < tab.nv; j++) {
             const double hj = tab.h[j];
-            const double *pj = tab.p[j] + i0;
+            const T *pj = tab.p[j] + i0;
 #pragma unroll
             for (int e = 0; e < kTile; e++) v[e] = v[e] - hj * pj[e * kBlock];
         }
@@ -1364,34 +1446,50 @@ struct ArnoldiOrth {
 };
 
 // GMRES: V(:,k+1) /= H(k+1,k) (lucky breakdown if 0)
+// (float ring: the unrounded vector is in VNEW; its quotient is rounded once into the ring slot and
+// the rounded values go to VCUR as doubles -- also after a lucky breakdown, which leaves VNEW as it is)
+template <class T>
 struct GmresNormalize {
     DState *st;
-    double *V;
+    T *V;
     int64_t N;
     double h;
-    double *v;
+    T *v;
     __device__ bool setup() {
         if (!st->running) return false;
         h = st->hk1;
-        v = V + st->k * N;
+        v = V + st->k * ring_ld<T>(N);
         return true;
     }
     __device__ void operator()(int64_t i) {
-        if (h != 0) v[i] = v[i] / h;
+        if constexpr (kRingF32<T>) {
+            double *work = ring_work(V, ring_slots(st, 0), N);
+            double x = work[i];
+            if (h != 0) x = x / h;
+            const float r = (float)x;
+            v[i] = r;
+            work[ring_ld<T>(N) + i] = (double)r;
+        } else {
+            if (h != 0) v[i] = v[i] / h;
+        }
     }
 };
 
 // DQGMRES: normalise V(:,kp1pos); PV(:,kpos) = (V(:,kpos) - sum H(j,kk) PV(:,jpos)) / H(k,2);
 // x = x + g(kpos)*PV(:,kpos); y = y - g(kpos)*PQ(:,kpos)   (cpdqgmres.m:222-265)
+// (float rings: vn is VNEW, whose quotient is rounded once into V's slot and copied to VCUR; the
+// direction is formed in double from ring reads, updates x and y unrounded, and is rounded once into PV)
+template <class T>
 struct DqgmresDirection {
     DState *st;
-    double *V, *PV, *xy;
+    T *V, *PV;
+    double *xy;
     int64_t n, N;
     int64_t kk, mem, M1, kpos, jlo;
     double h, hkk, gk;
-    double *vn, *pk;
-    const double *vk;
-    WinTab tab;
+    T *vn, *pk;
+    const T *vk;
+    WinTab<T> tab;
     __device__ bool setup() {
         if (!st->running) return false;
         kk = st->k, mem = st->mem, M1 = mem + 1;
@@ -1400,31 +1498,45 @@ struct DqgmresDirection {
         h = st->hk1;
         hkk = Hd(st, kk, 2);
         gk = st->g[kpos];
-        vn = V + (kk % M1) * N, vk = V + kpos * N, pk = PV + kpos * N;
-        __shared__ const double *tp[kWinTab];
+        const int64_t ld = ring_ld<T>(N);
+        vn = V + (kk % M1) * ld, vk = V + kpos * ld, pk = PV + kpos * ld;
+        __shared__ const T *tp[kWinTab];
         __shared__ double th[kWinTab];
         const int64_t nv = kk - jlo;
         tab.nv = nv <= kWinTab ? (int)nv : -1;
         for (int j = threadIdx.x; j < tab.nv; j += blockDim.x) {
             const int64_t jj = jlo + j;
-            tp[j] = PV + ((jj - 1) % M1) * N;
+            tp[j] = PV + ((jj - 1) % M1) * ld;
             th[j] = Hd(st, jj, 2 + kk - jj);
         }
         __syncthreads();
         tab.p = tp, tab.h = th;
         return true;
     }
+    // V(:, kp1pos) /= H(k+1, k)
+    __device__ void normalise(int64_t i) {
+        if constexpr (kRingF32<T>) {
+            double *work = ring_work(V, M1, N);
+            double x = work[i];
+            if (h != 0) x = x / h;
+            const float r = (float)x;
+            vn[i] = r;
+            work[ring_ld<T>(N) + i] = (double)r;
+        } else {
+            if (h != 0) vn[i] = vn[i] / h;
+        }
+    }
     __device__ void operator()(int64_t i) {
-        if (h != 0) vn[i] = vn[i] / h;
+        normalise(i);
         double pv = vk[i];
         if (tab.nv >= 0) {
 #pragma unroll 8
             for (int j = 0; j < tab.nv; j++) pv = pv - tab.h[j] * tab.p[j][i];
         } else {
-            for (int64_t j = jlo; j <= kk - 1; j++) pv = pv - Hd(st, j, 2 + kk - j) * PV[((j - 1) % M1) * N + i];
+            for (int64_t j = jlo; j <= kk - 1; j++) pv = pv - Hd(st, j, 2 + kk - j) * PV[((j - 1) % M1) * ring_ld<T>(N) + i];
         }
         pv = pv / hkk;
-        pk[i] = pv;
+        pk[i] = (T)pv;
         xy[i] = i < n ? xy[i] + gk * pv : xy[i] - gk * pv;
     }
     __device__ void tile(int64_t i0, int64_t Nn) {
@@ -1437,13 +1549,13 @@ struct DqgmresDirection {
 #pragma unroll
         for (int e = 0; e < kTile; e++) {
             const int64_t i = i0 + e * kBlock;
-            if (h != 0) vn[i] = vn[i] / h;
+            normalise(i);
             pv[e] = vk[i];
         }
-#pragma unroll 4
+#pragma unroll kWinUnroll<T>
         for (int j = 0; j < tab.nv; j++) {
             const double hj = tab.h[j];
-            const double *pj = tab.p[j] + i0;
+            const T *pj = tab.p[j] + i0;
 #pragma unroll
             for (int e = 0; e < kTile; e++) pv[e] = pv[e] - hj * pj[e * kBlock];
         }
@@ -1451,7 +1563,7 @@ struct DqgmresDirection {
         for (int e = 0; e < kTile; e++) {
             const int64_t i = i0 + e * kBlock;
             const double q = pv[e] / hkk;
-            pk[i] = q;
+            pk[i] = (T)q;
             xy[i] = i < n ? xy[i] + gk * q : xy[i] - gk * q;
         }
     }
@@ -1470,9 +1582,10 @@ struct GmresBackSolve {
     }
 };
 // x = x + V(:,1:k)*z ; q = 0 + Q(:,1:k)*z ; y = y - q   (cpgmres.m:258-260)
+template <class T>
 struct GmresUpdateX {
     DState *st;
-    const double *V;
+    const T *V;
     double *xy;
     int64_t n, N, k;
     __device__ bool setup() {
@@ -1481,7 +1594,7 @@ struct GmresUpdateX {
     }
     __device__ void operator()(int64_t i) {
         double t = 0.0;
-        for (int64_t j = 0; j < k; j++) t = t + V[j * N + i] * st->z[j];
+        for (int64_t j = 0; j < k; j++) t = t + V[j * ring_ld<T>(N) + i] * st->z[j];
         if (i < n) xy[i] = xy[i] + t;
         else xy[i] = xy[i] - (0.0 + t);
     }
@@ -1603,12 +1716,18 @@ struct SolveCore : SolveDriver {
         return vecs[i].p;
     }
     // the ring_next-th contiguous allocation of `count` N-vectors (slot rings, Arnoldi bases)
-    double *ring(size_t count) {
+    double *ring(size_t count) { return ring_of<double>(count); }
+    // ... of element type T, slots ring_ld<T>(N) apart (the buffers are counted in doubles)
+    template <class T>
+    T *ring_of(size_t count, size_t work = 0) {
         if (ring_next == rings.size()) rings.emplace_back();
         DBuf<double> &r = rings[ring_next++];
-        const size_t want = std::max<size_t>(count * (size_t)N, 1);  // a rank may own no rows
+        // (`work` more padded double vectors behind the last slot: ring_work)
+        const size_t elems = count * (size_t)ring_ld<T>(N);
+        const size_t want = std::max<size_t>((elems * sizeof(T) + sizeof(double) - 1) / sizeof(double) +
+                                                 work * (size_t)ring_ld<T>(N), 1);  // a rank may own no rows
         if (r.n != want) r.alloc(want);
-        return r.p;
+        return reinterpret_cast<T *>(r.p);
     }
     template <class T>
     static void ensure(DBuf<T> &b, size_t count) {
@@ -1740,8 +1859,32 @@ struct SolveCore : SolveDriver {
     // ------------------------------------------------------------------------------------------
     void minres_like(int kind, const double *b, double *xy, cpk_stats *stats);
     void cg(const double *b, double *xy, cpk_stats *stats);
+    template <class T>
     void gmres(const double *b, double *xy, cpk_stats *stats);
+    template <class T>
     void dqgmres(const double *b, double *xy, cpk_stats *stats);
+    // the basis ring of `count` slots; float: with VNEW and VCUR behind it (ring_work), at an
+    // address that is fixed while the solver is cached
+    template <class T>
+    T *basis_ring(size_t count) {
+        return ring_of<T>(count, kRingF32<T> ? 2 : 0);
+    }
+    // the Krylov product's input: the ring itself, or (float) VCUR behind the ring's `slots` slots
+    // at stride 0, see PolArnoldiSpmv.  The double overloads of this and the next two take the slot
+    // count only so that gmres<T> / dqgmres<T> make one call for both element types.
+    PolArnoldiSpmv arnoldi_pol(double *V, int64_t /*slots*/, int64_t ring) { return PolArnoldiSpmv{V, N, ring}; }
+    PolArnoldiSpmv arnoldi_pol(float *V, int64_t slots, int64_t ring) {
+        return PolArnoldiSpmv{ring_work(V, slots, N) + ring_ld<float>(N), 0, ring};
+    }
+    // where ArnoldiStart leaves the unnormalised V_1: its slot, or (float) VNEW
+    static double *start_vector(double *V, int64_t /*slots*/, int64_t /*N*/) { return V; }
+    static double *start_vector(float *V, int64_t slots, int64_t N) { return ring_work(V, slots, N); }
+    // V_1 from ArnoldiStart's sums: normalised in its slot, or (float) from VNEW into slot 0 and VCUR
+    void arnoldi_first(DState *st, double *V, int64_t) { launch_ew(c, N, NormalizeCopy{st, V, nullptr, 1, 0.0}); }
+    void arnoldi_first(DState *st, float *V, int64_t slots) {
+        double *work = ring_work(V, slots, N);
+        launch_ew(c, N, NormalizeRound{st, work, V, work + ring_ld<float>(N)});
+    }
 
     void finish_stats(cpk_stats *stats) {
         if (!stats) return;
@@ -1964,6 +2107,7 @@ void SolveCore::cg(const double *b, double *xy, cpk_stats *stats) {
 }
 
 // ---- cpgmres ----------------------------------------------------------------------------------
+template <class T>
 void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
     const int64_t R = (int64_t)restart;
     if (R < 1) throw Error(CPK_ERR_ARGS, "restart must be >= 1");
@@ -1979,7 +2123,7 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
     setup_state(hcap, R);
     loop_limit = std::max((double)R, itmax);  // a cycle runs to restart, past a smaller itmax (cpgmres.m:203)
     DState *st = dst.p;
-    double *V = ring((size_t)(R + 1));
+    T *V = basis_ring<T>((size_t)(R + 1));
     double *UT = vec(0), *Wv = vec(1), *TMP = vec(2);
     CPK_HIP(hipMemsetAsync(xy, 0, N * sizeof(double), c.stream));
     const double outermax = std::ceil(itmax / (double)R);
@@ -2001,8 +2145,8 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
             launch_ew(c, N, GmresRestartRhs{b, TMP, UT, n});
             M.apply(UT, n, Wv, nullptr);
         }
-        launch_ewred<2>(c, N, ArnoldiStart{st, Wv, UT, xy, V, n, outer > 1 ? 1 : 0, 0, outer == 1 ? 1 : 0});
-        launch_ew(c, N, NormalizeCopy{st, V, nullptr, 1, 0.0});
+        launch_ewred<2>(c, N, ArnoldiStart{st, Wv, UT, xy, start_vector(V, R + 1, N), n, outer > 1 ? 1 : 0, 0, outer == 1 ? 1 : 0});
+        arnoldi_first(st, V, R + 1);
         CPK_HIP(hipGetLastError());
         pull();
         if (h.err) raise_error();
@@ -2013,11 +2157,11 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
         }
         const int64_t base = (outer - 1) * R, hist0 = h.nh;
         auto body = [&]() {
-            launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, 0}, false, false, opp());
+            launch_krylov_spmv(c, AC, st, UT, n, arnoldi_pol(V, R + 1, 0), false, false, opp());
             M.apply(UT, n, Wv, &st->running);
             launch_arnoldi_dots(c, st, V, Wv, UT, n, N, 0, R);
-            launch_ewtred<2>(c, N, ArnoldiOrth{st, V, UT, n, N, 0, Window{}, nullptr});
-            launch_ew(c, N, GmresNormalize{st, V, N});
+            launch_ewtred<2>(c, N, ArnoldiOrth<T>{st, V, UT, n, N, 0, Window{}, nullptr});
+            launch_ew(c, N, GmresNormalize<T>{st, V, N});
         };
         loop(body, [&]() {  // printed iteration = (outer - 1) * restart + k  (cpgmres.m:252)
             if (h.nh <= printed) return;
@@ -2028,7 +2172,7 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
         });
         if (h.err) raise_error();
         launch_scalar(c, GmresBackSolve{st});
-        launch_ew(c, N, GmresUpdateX{st, V, xy, n, N, 0});
+        launch_ew(c, N, GmresUpdateX<T>{st, V, xy, n, N, 0});
         CPK_HIP(hipGetLastError());
         pull();
         finished = h.residNorm <= h.stopTol;
@@ -2041,6 +2185,7 @@ void SolveCore::gmres(const double *b, double *xy, cpk_stats *stats) {
 }
 
 // ---- cpdqgmres --------------------------------------------------------------------------------
+template <class T>
 void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
     const double memd = std::min(mem, itmax);  // cpdqgmres.m:125
     mem = std::max(1.0, memd);
@@ -2048,14 +2193,15 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
     const int64_t hcap = hist_capacity(itmax);
     setup_state(hcap, Mm);
     DState *st = dst.p;
-    double *V = ring((size_t)M1), *PV = ring((size_t)M1);
+    T *V = basis_ring<T>((size_t)M1);
+    T *PV = ring_of<T>((size_t)M1);
     double *UT = vec(0), *Wv = vec(1);
     CPK_HIP(hipMemsetAsync(xy, 0, N * sizeof(double), c.stream));
     if (print) printf("\n**** Constraint-preconditioned version of DQGMRES - mem = %lld ****\n\n", (long long)Mm);
     launch_set_concat(c, UT, b, n, m);
     M.apply(UT, N, Wv, nullptr);  // M * [u; t], t = 0 (cpdqgmres.m:154)
-    launch_ewred<2>(c, N, ArnoldiStart{st, Wv, UT, xy, V, n, 0, 1, 1});
-    launch_ew(c, N, NormalizeCopy{st, V, nullptr, 1, 0.0});
+    launch_ewred<2>(c, N, ArnoldiStart{st, Wv, UT, xy, start_vector(V, M1, N), n, 0, 1, 1});
+    arnoldi_first(st, V, M1);
     CPK_HIP(hipGetLastError());
     pull();
     if (h.err) {
@@ -2085,15 +2231,15 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
     if (prof) use_graph = false;
     auto body = [&]() {
         if (prof) mark();
-        launch_krylov_spmv(c, AC, st, UT, n, PolArnoldiSpmv{V, N, M1}, false, false, opp());
+        launch_krylov_spmv(c, AC, st, UT, n, arnoldi_pol(V, M1, M1), false, false, opp());
         if (prof) mark();
         M.apply(UT, n, Wv, &st->running);
         if (prof) mark();
         launch_arnoldi_dots(c, st, V, Wv, UT, n, N, M1, Mm);
         if (prof) mark();
-        launch_ewtred<2>(c, N, ArnoldiOrth{st, V, UT, n, N, M1, Window{}, nullptr});
+        launch_ewtred<2>(c, N, ArnoldiOrth<T>{st, V, UT, n, N, M1, Window{}, nullptr});
         if (prof) mark();
-        launch_ewt(c, N, DqgmresDirection{st, V, PV, xy, n, N});
+        launch_ewt(c, N, DqgmresDirection<T>{st, V, PV, xy, n, N});
         if (prof) {
             mark();
             // window sizes of this iteration (kernels: window(st, M1) and DqgmresDirection::setup)
@@ -2120,6 +2266,9 @@ void SolveCore::dqgmres(const double *b, double *xy, cpk_stats *stats) {
         }
         c.pass_ms[0] = (double)its;
         for (int q = 0; q < 5; q++) c.pass_ms[1 + q] = ms[q];
+        // (times and window sizes only: the byte model of each pass, for either ring element size,
+        // is applied by the reader -- bench.py s50_passes for the double ring, tools/basis_f32_timing.py
+        // pass_model for both)
         c.pass_ms[6] = wd, c.pass_ms[7] = wr;
         for (hipEvent_t e : evs) (void)hipEventDestroy(e);
     }
@@ -2166,6 +2315,9 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
                          double *d_xy, cpk_stats *stats, const OpHook *op) {
     if (method < CPK_CG || method > CPK_DQGMRES) throw Error(CPK_ERR_ARGS, "unknown method");
     if (op && (c.dist() || M.dist)) throw Error(CPK_ERR_UNSUPPORTED, "an operator-valued A on a distributed context");
+    const bool f32 = c.opts.basis_f32 && (method == CPK_GMRES || method == CPK_DQGMRES);
+    if (f32 && (c.dist() || M.dist))  // before anything is written
+        throw Error(CPK_ERR_UNSUPPORTED, "engine option basis_f32: cpgmres and cpdqgmres on a distributed context");
     CPK_HIP(hipEventRecord(c.ev0, c.stream));
     SolveCore &s = solver_for(c, M, AC, method, opts, d_b, d_xy, op);
     s.nbatch = 0;
@@ -2186,8 +2338,8 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
     case CPK_CGLANCZOS: s.minres_like(1, d_b, d_xy, stats); break;
     case CPK_SYMMLQ: s.minres_like(2, d_b, d_xy, stats); break;
     case CPK_CG: s.cg(d_b, d_xy, stats); break;
-    case CPK_GMRES: s.gmres(d_b, d_xy, stats); break;
-    case CPK_DQGMRES: s.dqgmres(d_b, d_xy, stats); break;
+    case CPK_GMRES: f32 ? s.gmres<float>(d_b, d_xy, stats) : s.gmres<double>(d_b, d_xy, stats); break;
+    case CPK_DQGMRES: f32 ? s.dqgmres<float>(d_b, d_xy, stats) : s.dqgmres<double>(d_b, d_xy, stats); break;
     }
     // keyed as the NEXT call will ask for it: a new solver's first run may have grown the context's
     // reduction workspace before it captured its graphs (setup_state; cpgmres and cpdqgmres take one
@@ -2203,7 +2355,7 @@ void method_solve_device(Ctx &c, int method, const double *d_b, const DMat &AC, 
         float ms = 0;
         CPK_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
         stats->loop_ms = ms;
-        stats->bytes_moved = method_bytes(method, AC, M, stats->niters, opts, op);
+        stats->bytes_moved = method_bytes(method, AC, M, stats->niters, opts, op, f32);
     }
 }
 
@@ -2310,6 +2462,20 @@ struct DebugDot {  // out[j] = <A(:, j), B(:, j)>
         for (int j = 0; j < NV; j++) out[j] = tot[j];
     }
 };
+// cpk_debug_arnoldi_step under basis_f32: a ring of N-vectors between its double image (slots N
+// apart) and the float ring (slots ldf apart); down: round to float, else convert back exactly
+struct RingConvert {
+    double *d;
+    float *f;
+    int64_t N, ldf;
+    bool down;
+    __device__ bool setup() { return true; }
+    __device__ void operator()(int64_t q) {
+        const int64_t col = q / N, i = q - col * N;
+        if (down) f[col * ldf + i] = (float)d[q];
+        else d[q] = (double)f[col * ldf + i];
+    }
+};
 struct DebugXnorm2 {
     const double *a, *b;
     double *out;
@@ -2351,6 +2517,8 @@ void debug_xnorm2(Ctx &c, int64_t n, const double *d_a, const double *d_b, doubl
 // arnoldi_sizes / size_reductions, as setup_state sizes them.
 void debug_arnoldi_step(Ctx &c, cpk_arnoldi_step &s, double *d_V, double *d_PV, double *d_xy, const double *d_w,
                         const double *d_ut) {
+    if (c.opts.basis_f32 && c.dist())  // with the argument checks: before any device call
+        throw Error(CPK_ERR_UNSUPPORTED, "engine option basis_f32: the Arnoldi step on a distributed context");
     const bool dq = s.method == CPK_DQGMRES;
     const int64_t N = s.N, n = s.n, maxv = s.win, ring = dq ? s.win + 1 : 0;
     const ArnoldiSizes z = arnoldi_sizes(s.method, s.win, s.win);
@@ -2369,14 +2537,39 @@ void debug_arnoldi_step(Ctx &c, cpk_arnoldi_step &s, double *d_V, double *d_PV, 
     h.H = H.p, h.c = cv.p, h.s = sv.p, h.g = gv.p, h.z = zv.p;
     CPK_HIP(hipMemcpy(dst.p, &h, sizeof h, hipMemcpyHostToDevice));
     DState *st = dst.p;
-    launch_arnoldi_dots(c, st, d_V, d_w, d_ut, n, N, ring, maxv, s.grid);
+    // basis_f32: the caller's rings rounded to float (slots ring_ld<float>(N) apart), the float launches,
+    // and the rings back as doubles; VNEW and VCUR are this call's own
+    DBuf<float> fV, fPV;
+    const int64_t ldf = ring_ld<float>(N), cols = s.win + 1;
+    const bool f32 = c.opts.basis_f32;
+    auto convert = [&](bool down) {
+        const int64_t cnt = N * cols;
+        if (!cnt) return;
+        launch_ew(c, cnt, RingConvert{d_V, fV.p, N, ldf, down});
+        if (dq) launch_ew(c, cnt, RingConvert{d_PV, fPV.p, N, ldf, down});
+    };
+    if (f32) {
+        // (the basis ring with VNEW and VCUR behind it, ring_work: 2 ldf doubles = 4 ldf floats)
+        fV.alloc((size_t)std::max<int64_t>(ldf * (cols + 4), 1)), fPV.alloc((size_t)std::max<int64_t>(dq ? ldf * cols : 1, 1));
+        convert(true);
+        launch_arnoldi_dots(c, st, fV.p, d_w, d_ut, n, N, ring, maxv, s.grid);
+    } else {
+        launch_arnoldi_dots(c, st, d_V, d_w, d_ut, n, N, ring, maxv, s.grid);
+    }
     if (s.H_dots) {
         CPK_HIP(hipMemcpyAsync(s.H_dots, H.p, z.H * sizeof(double), hipMemcpyDeviceToHost, c.stream));
         CPK_HIP(hipStreamSynchronize(c.stream));
     }
-    launch_ewtred<2>(c, N, ArnoldiOrth{st, d_V, d_ut, n, N, ring, Window{}, nullptr});
-    if (dq) launch_ewt(c, N, DqgmresDirection{st, d_V, d_PV, d_xy, n, N});
-    else launch_ew(c, N, GmresNormalize{st, d_V, N});
+    if (f32) {
+        launch_ewtred<2>(c, N, ArnoldiOrth<float>{st, fV.p, d_ut, n, N, ring, Window{}, nullptr});
+        if (dq) launch_ewt(c, N, DqgmresDirection<float>{st, fV.p, fPV.p, d_xy, n, N});
+        else launch_ew(c, N, GmresNormalize<float>{st, fV.p, N});
+        convert(false);
+    } else {
+        launch_ewtred<2>(c, N, ArnoldiOrth<double>{st, d_V, d_ut, n, N, ring, Window{}, nullptr});
+        if (dq) launch_ewt(c, N, DqgmresDirection<double>{st, d_V, d_PV, d_xy, n, N});
+        else launch_ew(c, N, GmresNormalize<double>{st, d_V, N});
+    }
     CPK_HIP(hipGetLastError());
     CPK_HIP(hipMemcpyAsync(&h, dst.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
     CPK_HIP(hipStreamSynchronize(c.stream));
@@ -2466,7 +2659,7 @@ void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *
 // Algorithmic HBM bytes of one method call: per iteration the Krylov SpMV,
 // the preconditioner apply and the streaming vector kernels, counted as ideal single touches.
 double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts,
-                    const OpHook *op) {
+                    const OpHook *op, bool basis_f32) {
     const double N = (double)M.N;
     // an operator-valued A: AC is blkdiag(0, C), plus the gather (16 n) and the read of fn's output (8 n)
     const double spmv = 12.0 * AC.nnz + 4.0 * (N + 1) + 8.0 * N /*x*/ + 8.0 * N /*y*/ + (op ? 24.0 * M.n : 0.0);
@@ -2486,6 +2679,12 @@ double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters,
         if (opts && method == CPK_GMRES && opts->has_restart) w = opts->restart;
         if (opts && method == CPK_DQGMRES && opts->has_mem) w = opts->mem;
         vec = 8 * N * (3 + w / 2 + w / 2 + 3);
+        // (3 streams around the dots, a mean window of w / 2 vectors in the dots and again in the
+        // orthogonalisation, 3 streams around the orthogonalisation)
+        // basis_f32, the mode this solve ran in: the same count with the window vectors at 4 bytes
+        // and a slot's stride padded to 64 floats, and one more double stream, VCUR, which the
+        // normalisation writes beside the ring slot
+        if (basis_f32) vec = 4.0 * (double)ring_ld<float>(M.N) * (w / 2 + w / 2) + 8 * N * (3 + 3 + 1);
         break;
     }
     }

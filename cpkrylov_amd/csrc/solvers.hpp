@@ -83,6 +83,7 @@ void debug_arnoldi_step(Ctx &c, cpk_arnoldi_step &s, double *d_V, double *d_PV, 
 void profile_kernels(Ctx &c, const DMat &AC, Precond &M, int reps, cpk_profile *out);
 // op: AC is blkdiag(0, C); the product's model adds the gather and the epilogue's read of fn's
 // output (24 n), cpminres runs unfused, and fn's own traffic is unknown and not counted
+// basis_f32: the solve ran with the float basis (cpgmres / cpdqgmres only)
 double method_bytes(int method, const DMat &AC, const Precond &M, int64_t iters, const cpk_opts *opts,
-                    const OpHook *op = nullptr);
+                    const OpHook *op = nullptr, bool basis_f32 = false);
 }  // namespace cpk

@@ -139,8 +139,8 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * Names: sweep ("rows,cap,threads[,rows,cap,threads[,sub0]]"; unset, each path has its own
  * default: a distributed context reports and uses the distributed one), split_tol, pivot_min
  * (delta, a finite number >= 0, default 0 = off: a pivot of the LDL' whose expected sign s gives
- * s * d < delta is replaced by s * delta, see cpk_pc_factor_report; the one option besides
- * exact_dots that changes results; read at every cpk_pc_create[_hint], cpk_pc_refactor and
+ * s * d < delta is replaced by s * delta, see cpk_pc_factor_report; with exact_dots and
+ * basis_f32 one of the three options that change results; read at every cpk_pc_create[_hint], cpk_pc_refactor and
  * cpk_analyze), host_factor,
  * no_pipe, no_upper, no_col16, no_dataflow, all_dataflow, no_colsweep, all_colsweep, no_rowspan, all_rowspan
  * (the upper rounds' row-span level loop: never / on every eligible block instead of where the host
@@ -158,6 +158,23 @@ int cpk_ctx_create_sim(int device, cpk_simgroup group, int rank, int nranks, cpk
  * profile_passes (diagnostic: cpdqgmres runs eagerly with events between its passes, read by
  * cpk_debug_pass_times), fail_inject ("rank:site[:n]", site setup / batch / chain: a test hook
  * that makes one rank of a distributed solve fail at that point).
+ * basis_f32 ("0"/"1", default 0, environment CPK_BASIS_F32; read at every solve; with exact_dots and
+ * pivot_min the third option that changes results): cpgmres and cpdqgmres keep their rings (V, and PV
+ * for cpdqgmres) as float arrays, slots padded to 64 floats.  One rule defines every bit.  A basis
+ * vector [V(:,j); Q(:,j)] or a direction [PV(:,j); PQ(:,j)] is built and normalised in double, as
+ * without the option, and its final value is rounded ONCE to float (IEEE round to nearest even,
+ * subnormals kept, beyond the float range +-inf) when it is stored in its ring slot.  Every read of a
+ * ring slot converts the float exactly to double: the window sums, the orthogonalisation, the
+ * Q(:,k+1) = Q(:,k) - w recurrence, the direction recurrence, cpgmres's update of x and y, and the
+ * vector the Krylov product multiplies.  The vector under construction stays in double, so
+ * H(k+1,k) = sqrt(<u, vnew> + <t, qnew>) is taken on the unrounded vector (a stored vector's
+ * form-norm is 1 to about 2^-24 only), and cpdqgmres updates x and y with the unrounded direction.
+ * Rotations, SymGivens, g, the stop tests, the histories and the errors are unchanged.  The rounding
+ * of the basis reaches H(k+1,k)^2: where that is rounding noise (a residual that collapses in a step)
+ * its sign is arbitrary at 2^-24 instead of 2^-53 and the methods stop with CPK_ERR_INDEFINITE more
+ * often (DESIGN.md "Compressed basis").  The other four methods, the block solves and the
+ * preconditioner do not see the option.  On a distributed context or preconditioner cpgmres and
+ * cpdqgmres answer CPK_ERR_UNSUPPORTED before anything is written while it is set.
  * Booleans as "0"/"1".  A distributed preconditioner allgathers a hash of its plan and of every
  * option but fail_inject at creation and fails (CPK_ERR_ARGS) on every rank unless all ranks
  * agree. */
@@ -776,7 +793,11 @@ int cpk_debug_xnorm2(cpk_ctx ctx, int64_t n, const double *a, const double *b, d
  *   stop, err, err_val, err_iter, nh  out (err = 4: the squared norm err_val of the new vector is negative)
  * On a context of several ranks the call is collective: every rank passes its local rows and its
  * own n, and receives the same scalars.  A window wider than the distributed reduction buffer
- * (2 win sums > 4096): CPK_ERR_UNSUPPORTED.  Bad arguments: CPK_ERR_ARGS, before any device call. */
+ * (2 win sums > 4096): CPK_ERR_UNSUPPORTED.  Bad arguments: CPK_ERR_ARGS, before any device call.
+ * Under engine option basis_f32 the call rounds V and PV to float on upload (every slot), runs the
+ * float launches and returns the rings as doubles, so every slot comes back as its float image and the
+ * written slots hold the once-rounded vectors; the struct and its meaning are unchanged.  A context
+ * of several ranks then answers CPK_ERR_UNSUPPORTED. */
 typedef struct {
     int method, running, grid;
     int64_t n, N, win, kk, itmax;
